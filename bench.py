@@ -5,7 +5,11 @@ synthetic requests per replica), one DP replica per GPU by default.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--concurrency 64]
                   [--prompt-len 512] [--output-len 256] [--model llama3-8b]
-                  [--tp 1]
+                  [--tp 1] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs if --dump-outputs is given and prints the result line. Measurements
+beyond the headline figure belong behind --full (none today).
 
 For N > 1 launch one rank per GPU (torch.distributed.run). With --tp 1 the
 ranks are independent replicas (weak scaling: per-GPU work is fixed) that only
@@ -65,6 +69,13 @@ def parse():
                     help="single-GPU simulation of ONE rank of a TP group of this degree: the rank's weight / "
                          "KV shards and kernels, collectives replaced by local reductions (not a TP measurement: "
                          "xGMI time is excluded; reported with parallelism 'tpN-shard-sim')")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float64): same arguments, same inputs, so two builds compare output "
+                         "for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure (nothing today: a "
+                         "plain run already does only setup, warmup, the timed steps and the result line)")
     return ap.parse_args()
 
 
@@ -116,6 +127,23 @@ def prompt_gemm(eng) -> str:
     from xgserve.models import llama
     return "gemm_pf " + ", ".join(f"{k} {'+'.join(f'{lo}-{hi}' for lo, hi in ws)}"
                                   for k, ws in sorted(llama.PF_WINDOWS.items()) if ws) + " tokens"
+
+
+def dump_outputs(out_dir: str, rank: int, outs) -> None:
+    """--dump-outputs: the last timed step's outputs as its caller received them, one
+    row per new token in request order: (request number in submission order, index of
+    the token in that request's output, token id, 1 if the request finished in this
+    step). Requests, prompts and weights are seeded, so the same arguments give the
+    same rows on every run of the same build. Rank 0 writes last_step_tokens.npy,
+    every other replica's leader last_step_tokens_rank<r>.npy."""
+    rows = []
+    for o in outs:
+        n = int(o.request_id.rsplit("-", 1)[1])
+        first = o.completion_tokens - len(o.new_token_ids)
+        rows += [(n, first + j, tok, int(o.finished)) for j, tok in enumerate(o.new_token_ids)]
+    arr = np.asarray(sorted(rows), dtype=np.float64).reshape(-1, 4)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "last_step_tokens.npy" if rank == 0 else f"last_step_tokens_rank{rank}.npy"), arr)
 
 
 def preflight(st, world: int, tp: int, dev, eng) -> dict:
@@ -269,6 +297,7 @@ def main():
         initial.append(f"r{rank}-{counter[0] - 1}")
 
     step_log = [] if os.environ.get("XGS_STEP_LOG") else None
+    last_outs = [[]]  # what the most recent step returned (--dump-outputs)
 
     def run_step():
         if step_log is not None:
@@ -276,6 +305,7 @@ def main():
             p0 = dict(eng._timing) if eng._timing is not None else None
         outs = eng.step()
         now = time.perf_counter()
+        last_outs[0] = outs
         if step_log is not None:
             c1 = eng.stats_counters
             step_log.append((round(1000 * (now - t0), 3), c1["prefill_tokens_computed"] - c0["prefill_tokens_computed"],
@@ -330,6 +360,8 @@ def main():
             for i, e in enumerate(step_log):
                 f.write(json.dumps({"i": i, "timed": i >= a.warmup, "ms": e[0], "prefill_tokens": e[1],
                                     "decode_step": e[2], "gen_tokens": e[3], "phases_ms": e[4]}) + "\n")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, last_outs[0])
     ttfts = [first_tok[r] - arrival[r] for r in first_tok if r not in first_before]
     p50_local = float(np.median(ttfts)) if ttfts else float("nan")
 

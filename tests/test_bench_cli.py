@@ -81,6 +81,26 @@ def test_bench_single_gpu_default_unchanged():
     _check_contract(r, 1, "llama-tiny", "dp1", 1)
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's tokens as float64 .npy, the same rows
+    for the same arguments on every run; --full is accepted and a plain run's result
+    line keeps its keys."""
+    import numpy as np
+    arrs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        r = _run(1, "--model", "llama-tiny", "--dump-outputs", str(tmp_path / name), *extra, launcher=False)
+        _check_contract(r, 1, "llama-tiny", "dp1", 1)
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["last_step_tokens.npy"]
+        arrs.append(np.load(tmp_path / name / files[0]))
+    a, b = arrs
+    assert a.dtype == np.float64 and a.ndim == 2 and a.shape[1] == 4
+    # 2 concurrent requests: the step returned 1..2 tokens per request (see _check_contract)
+    assert 1 <= a.shape[0] <= 4
+    assert (a[:, 2] >= 0).all() and (a[:, 2] == np.floor(a[:, 2])).all()
+    assert np.array_equal(a, b)
+
+
 def test_bench_rejects_world_mismatch():
     env = dict(_env(), WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", *SMALL, "--model", "llama-tiny"],
@@ -104,11 +124,13 @@ def _check_contract(r, nproc, model, par, tp):
     assert 0 < r["value"] <= 2 * cfg["global_batch"] * 1000.0 / r["ms_per_step"] + 1e-6
 
 
-def test_numa_cpulist_parsing_and_noop_without_gpu():
+def test_numa_cpulist_parsing_and_noop_without_gpu(tmp_path, monkeypatch):
     from xgserve.parallel import affinity as A
     assert A._parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
     assert A._parse_cpulist("") == set()
-    # no KFD GPU nodes in this container: nothing to bind, affinity untouched
+    # a KFD topology without GPU nodes (an empty one, whatever the host has): nothing to
+    # bind, affinity untouched
+    monkeypatch.setattr(A, "_KFD", str(tmp_path))
     import os
     before = os.sched_getaffinity(0)
     assert A.bind_to_gpu_numa(0) is None

@@ -19,6 +19,7 @@
 """
 from __future__ import annotations
 
+import gc
 import logging
 import math
 import os
@@ -308,6 +309,21 @@ class ModelRunner:
     def capture_graphs(self):
         if not self.use_graphs or not self.graph_bs:
             return
+        # An engine that was dropped earlier is a reference cycle: its graphs and their
+        # pool live until the cycle collector runs. A collection in the middle of a
+        # capture would destroy them inside the capturing region (graph destruction and
+        # the pool's frees are not allowed there) and abort the process, so collect now
+        # and hold automatic collections off until the last capture has ended.
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            self._capture_graphs()
+        finally:
+            if gc_was_enabled:
+                gc.enable()
+
+    def _capture_graphs(self):
         torch.cuda.synchronize()
         # neutral inputs: padding rows (no KV writes, no attention work)
         self.g_slot.fill_(-1)
