@@ -2,7 +2,7 @@
 """Fused decode-layer GEMM forms vs their plain forms at small M, graph-timed with
 cold weights (a ring of weight copies larger than the Infinity Cache):
 
-  qkv / gate_up : m64_linear on a pre-normalised x   vs  m64_norm_linear (RMSNorm as
+  qkv / gate_up : m64_linear on a pre-normalised x   vs  m64_linear with stats (RMSNorm as
                   a row scale from per-tile statistics, ss_n of them)
   o / down      : m64_linear (partials)               vs  m64_resid_linear (GG_RESID:
                   residual add + next statistics in the launch)
@@ -85,7 +85,7 @@ def main():
                         continue
                     ss = torch.rand(n_parts, M, device=dev) * K / n_parts
                     st = L.RowStats(ss, n_parts, M)
-                    rows[f"norm{n_parts}"] = graph_time([lambda w=w, st=st: L.m64_norm_linear(x, w, mode, st, 1e-5)
+                    rows[f"norm{n_parts}"] = graph_time([lambda w=w, st=st: L.m64_linear(x, w, mode, stats=st, eps=1e-5)
                                                          for w in ws])
             else:
                 rw = L.ResidWorkspace(4, max(64, M), N, dev)
@@ -103,8 +103,8 @@ def main():
                                 if kind == "norm":
                                     n_parts = 128 if M <= 16 else 64
                                     st = L.RowStats(torch.rand(n_parts, M, device=dev) * K / n_parts, n_parts, M)
-                                    us = graph_time([lambda w=w, st=st, p=p: L.m64_norm_linear(x, w, mode, st, 1e-5,
-                                                                                               plan=p) for w in ws])
+                                    us = graph_time([lambda w=w, st=st, p=p: L.m64_linear(
+                                        x, w, mode, nw=p[0], split_k=p[1], cfg=p[2], stats=st, eps=1e-5) for w in ws])
                                 else:
                                     us = graph_time([lambda w=w, p=p: L.m64_resid_linear(x, w, resid, rw, 1, 1e-5,
                                                                                          plan=p) for w in ws])

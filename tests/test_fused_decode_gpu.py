@@ -13,7 +13,7 @@ from xgserve import ops
 from xgserve.ops import _native
 from xgserve.ops import linear as lin
 from xgserve.ops.linear import (MODE_PARTIAL, MODE_SILU, PendingSum, ResidWorkspace, RowStats, interleave_gate_up,
-                                m64_norm_linear, m64_resid_linear)
+                                m64_linear, m64_resid_linear)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -42,10 +42,10 @@ def test_norm_linear_row_scale(M, n_parts):
     st = RowStats(sq.view(M, n_parts, -1).sum(-1).t().contiguous(), n_parts, M)
     h = x.float() * torch.rsqrt(sq.sum(-1, keepdim=True) / K + 1e-5)
     w = rnd(6144, K, scale=0.02)
-    pend = m64_norm_linear(x, w, MODE_PARTIAL, st, 1e-5)
+    pend = m64_linear(x, w, MODE_PARTIAL, stats=st, eps=1e-5)
     assert rel_err(pend.part.sum(0), h @ w.float().t()) < 2e-3
     g, u = rnd(14336, K, scale=0.02), rnd(14336, K, scale=0.02)
-    y = m64_norm_linear(x, interleave_gate_up(g, u), MODE_SILU, st, 1e-5)
+    y = m64_linear(x, interleave_gate_up(g, u), MODE_SILU, stats=st, eps=1e-5)
     ref = F.silu(h @ g.float().t()) * (h @ u.float().t())
     assert rel_err(y, ref) < 1e-2
 
@@ -64,11 +64,11 @@ def test_norm_linear_128_partial_sums(M, n_parts, N, K, mode):
     h = x.float() * torch.rsqrt(sq.sum(-1, keepdim=True) / K + 1e-5)
     if mode == MODE_PARTIAL:
         w = rnd(N, K, scale=0.02)
-        pend = m64_norm_linear(x, w, MODE_PARTIAL, st, 1e-5)
+        pend = m64_linear(x, w, MODE_PARTIAL, stats=st, eps=1e-5)
         assert rel_err(pend.part.sum(0), h @ w.float().t()) < 2e-3
     else:
         g, u = rnd(N // 2, K, scale=0.02), rnd(N // 2, K, scale=0.02)
-        y = m64_norm_linear(x, interleave_gate_up(g, u), MODE_SILU, st, 1e-5)
+        y = m64_linear(x, interleave_gate_up(g, u), MODE_SILU, stats=st, eps=1e-5)
         assert rel_err(y, F.silu(h @ g.float().t()) * (h @ u.float().t())) < 1e-2
 
 
@@ -94,7 +94,7 @@ def test_split_silu_and_wide_tile(M, S, cfg, normed):
     try:
         for _ in range(2):
             if normed:
-                y = m64_norm_linear(x, w, MODE_SILU, st, 1e-5)
+                y = m64_linear(x, w, MODE_SILU, stats=st, eps=1e-5)
             else:
                 y = lin.m64_linear(x, w, MODE_SILU)
             assert rel_err(y, ref) < 1e-2
@@ -208,6 +208,25 @@ def llama_small():
     from xgserve.models import build_model, get_config
     cfg = replace(get_config("llama3-8b"), num_layers=2, name="llama3-8b-2l")
     return build_model(cfg, device="cuda:0", seed=3)
+
+
+@pytest.mark.parametrize("M", [1, 17])
+@pytest.mark.parametrize("name,mode", [("qkv", MODE_PARTIAL), ("gate_up", MODE_SILU)])
+def test_m64_linear_stats_matches_prenormed(llama_small, M, name, mode):
+    """m64_linear with `stats` (the RMSNorm as an epilogue row scale of the raw x) against
+    the same wrapper on rmsnorm(x), on the 8B QKV [6144, 4096] and gate_up [28672, 4096]."""
+    w = getattr(llama_small.layers[0], name)
+    K = w.shape[1]
+    assert tuple(w.shape) == ((6144, 4096) if name == "qkv" else (28672, 4096))
+    x = rnd(M, K)
+    st = RowStats((x.float() ** 2).view(M, 4, -1).sum(-1).t().contiguous(), 4, M)
+    got = m64_linear(x, w, mode, stats=st, eps=1e-5)
+    ref = m64_linear(ops.rmsnorm(x, torch.ones(K, device=DEV, dtype=torch.bfloat16), 1e-5), w, mode)
+    if mode == MODE_PARTIAL:
+        assert rel_err(got.part.sum(0), ref.part.sum(0)) < 2e-3
+    else:
+        assert got.shape == ref.shape == (M, w.shape[0] // 2)
+        assert rel_err(got, ref) < 1e-2
 
 
 @pytest.mark.parametrize("fused", [True, False])

@@ -17,14 +17,22 @@ for prefill-sized ones) or forced with "alltoall" / "allreduce":
     and all-gathers the slices;
   * "allreduce": every rank runs its local experts on all tokens and one
     all-reduce sums the partial outputs.
-Per layer the hot path is: fused_add_rmsnorm (K1) -> QKV GEMM -> rope+KV append
-(K2/K4) -> paged decode / varlen prefill attention (K6/K5) -> o GEMM -> AR ->
-fused_add_rmsnorm -> gate_up GEMM -> SiLU-gate (K3) -> down GEMM -> AR.
+Per layer the hot path is one chain (LlamaLayer.forward): add + RMSNorm -> QKV GEMM
+-> RoPE + KV append + paged decode / varlen prefill attention -> O GEMM (-> AR) ->
+add + RMSNorm -> gate_up GEMM with the SiLU gate -> down GEMM (-> AR). LayerDispatch
+picks each projection's GEMM kernel from the step size: gemm_w8 (quantized copies)
+or gemm_m64g up to 64 tokens (skinny_gemm up to 16 where gemm_m64g has no small-M
+plan), gemm_mw up to 320, gemm_pf inside its measured windows, else the library.
+The HIP GEMMs hand split-K partials to their consumer (the attention prologue or
+add + RMSNorm) and gate inside gate_up; the library GEMMs are followed by rope_cache
+and silu_and_mul launches. Pure-decode steps of dense and MoE models normally take
+the fused decode layer instead (forward_fused, below).
 """
 from __future__ import annotations
 
+import functools
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -34,10 +42,10 @@ from .. import ops, tune
 from ..parallel import comm
 from ..parallel.state import get_state
 from ..ops import linear as linear_mod
-from ..ops.linear import (MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M, W8_MIN_ELEMS, ResidWorkspace, RowStats,
-                          lm_head_linear, m64_ar_resid_linear, m64_linear, m64_norm_linear, m64_plan,
+from ..ops.linear import (MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M, W8_MIN_ELEMS, PendingSum, ResidWorkspace,
+                          RowStats, lm_head_linear, m64_ar_resid_linear, m64_linear, m64_plan,
                           m64_resid_linear,
-                          mw_linear, mw_plan, pf_linear, pf_plan, pick_split,
+                          mw_linear, mw_plan, pf_linear, pf_plan,
                           quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
                           w8_plan, WQ_FORMATS)
 from .base import AttnMeta, PagedAttention, init_weight, kv_head_range, local_heads, shard
@@ -45,8 +53,8 @@ from .config import ModelConfig
 
 
 
-FAST_M_SMALL = 16   # tokens per step handled entirely by the streaming skinny GEMM
-FAST_M_SLAB = 64    # tokens per step for the O-projection slab kernel
+FAST_M_SMALL = 16   # tokens per step on the streaming skinny GEMM (shapes without a small-M gemm_m64g plan)
+FAST_M_SLAB = 64    # tokens per step on gemm_m64g (and on gemm_w8)
 # Fused decode layer (dense Llama, TP=1, pure-decode steps of <= 64 tokens): the
 # RMSNorms become GEMM epilogue row scales (norm weights folded into W), the
 # residual adds + norm statistics run inside the O / down GEMM launches and the
@@ -118,6 +126,93 @@ EP_EXACT_MIN_PAIRS = tune.get_int("ep_exact_min_pairs", 256)
 EP_AR_MAX_TOKENS = 64
 
 
+PROJECTIONS = ("qkv", "o", "gate_up", "down")
+
+
+class Step(NamedTuple):
+    """The GEMM kernel family of each projection at one step -- "w8", "skinny", "m64",
+    "mw", "pf" (HIP: QKV / O / down as split-K partials into their consumers, the SiLU
+    gate inside gate_up) or "lib" (library GEMM, bf16 out) -- and the attention entry:
+    "fused_decode" / "from_partials" for QKV partials, "rope" for a QKV tensor. MoE
+    layers run their experts (LlamaLayer.mlp) in place of gate_up / down."""
+    qkv: str
+    o: str
+    gate_up: str
+    down: str
+    attn: str
+
+
+def _uniform(family: str, attn: str = "from_partials") -> Step:
+    return Step(family, family, family, family, attn)
+
+
+SKINNY, M64, M64_FUSED_QKV, MW, LIB = (_uniform("skinny"), _uniform("m64"), _uniform("m64", "fused_decode"),
+                                       _uniform("mw"), _uniform("lib", "rope"))
+
+
+@functools.lru_cache(maxsize=None)  # (eager prompt steps ask once per layer; T <= PF_MAX_M bounds it)
+def _pf_step(T: int) -> Step:
+    """gemm_pf for the projections whose measured window holds T, the library for the rest."""
+    use_pf = pf_projections(T)
+    if not use_pf:
+        return LIB
+    return Step(*("pf" if n in use_pf else "lib" for n in PROJECTIONS), "from_partials" if "qkv" in use_pf else "rope")
+
+
+class LayerDispatch:
+    """Which kernels a layer of these dimensions runs at a (T tokens, num_decodes)
+    step of the unfused chain. Pure: built from the local projection shapes
+    (qkv [Nqkv, H], o [H, HqD], gate_up [2 Fl, H], down [H, Fl]; MoE layers have no
+    Fl), the TP degree and whether the layer is on a GPU; no tensors, no device
+    calls. m64_plan has a plan at 16 < M <= 64 for every shape that passes `fast_ok`
+    (tests/test_layer_dispatch.py pins it), so such a layer has no library arm below
+    65 tokens."""
+
+    def __init__(self, Nqkv: int, H: int, HqD: int, Fl: int, moe: bool, tp: int, on_gpu: bool, attn_fq_ok: bool):
+        self.attn_fq_ok = attn_fq_ok    # the decode attention kernel's fused-QKV form fits the head layout
+        self.quantized: Optional[Step] = None
+        self.fast_ok = on_gpu and H % 256 == 0 and HqD % 256 == 0 and Nqkv % 64 == 0 and (moe or Fl % 256 == 0)
+        shapes = ((Nqkv, H, MODE_PARTIAL), (H, HqD, MODE_PARTIAL))
+        if not moe:
+            shapes += ((2 * Fl, H, MODE_SILU), (H, Fl, MODE_PARTIAL))
+        # M <= 16 on gemm_m64g too, when every projection has a measured small-M plan
+        self.m64_small_ok = self.fast_ok and all(m64_plan(1, n, k, mode) is not None for n, k, mode in shapes)
+        # 64 < M <= MW_MAX_TOKENS: gemm_mw for every projection (MoE layers: the attention
+        # projections; the experts stay on the grouped gemm_m64g)
+        self.mw_ok = self.fast_ok and MW_MAX_TOKENS > FAST_M_SLAB and all(
+            mw_plan(MW_MAX_TOKENS, n, k, mode) is not None and mw_plan(FAST_M_SLAB + 1, n, k, mode) is not None
+            for n, k, mode in shapes)
+        # T > MW_MAX_TOKENS on TP = 1: gemm_pf inside PF_WINDOWS
+        self.pf_ok = self.fast_ok and PF_MAX_M > 0 and tp == 1 and all(
+            pf_plan(PF_MAX_M, n, k, mode) is not None for n, k, mode in shapes)
+
+    @classmethod
+    def for_layer(cls, cfg: ModelConfig, tp: int, on_gpu: bool) -> "LayerDispatch":
+        Hq, Hkv = local_heads(cfg, tp)
+        D, moe = cfg.head_dim, cfg.arch == "mixtral"
+        # the decode attention kernel's fused-QKV form: D = 128, GQA groups of 1/2/4/8
+        attn_fq_ok = on_gpu and D == 128 and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
+        return cls((Hq + 2 * Hkv) * D, cfg.hidden_size, Hq * D, 0 if moe else cfg.intermediate_size // tp, moe, tp,
+                   on_gpu, attn_fq_ok)
+
+    def set_quantized(self, names) -> None:
+        """The projections in `names` have fp8 / int8 / int4 copies (gemm_w8, T <= W8_MAX_M);
+        the others run their bf16 weight on gemm_m64g there."""
+        self.quantized = Step(*("w8" if n in names else "m64" for n in PROJECTIONS), "from_partials")
+
+    def select(self, T: int, num_decodes: int) -> Step:
+        if self.quantized is not None and T <= W8_MAX_M:
+            return self.quantized
+        if self.fast_ok and T <= FAST_M_SLAB:
+            if T <= FAST_M_SMALL and not self.m64_small_ok:
+                return SKINNY
+            # pure-decode steps reduce the QKV partials + RoPE + KV append in the attention prologue
+            return M64_FUSED_QKV if (T == num_decodes and self.attn_fq_ok) else M64
+        if self.mw_ok and T <= MW_MAX_TOKENS:
+            return MW
+        return _pf_step(T) if (self.pf_ok and T <= PF_MAX_M) else LIB
+
+
 @torch.no_grad()
 def _fold_norm(w: torch.Tensor, norm: torch.Tensor) -> None:
     """W[:, k] *= norm[k] (one bf16 rounding), norm <- 1: rmsnorm(x, g) @ W^T ==
@@ -160,59 +255,38 @@ class LlamaLayer(nn.Module):
             self.gate_up = _p(z(2 * Fl, H))
             self.down = _p(z(H, Fl))
         self.attn = PagedAttention(Hq, Hkv, D)
-        # the decode attention kernel's fused-QKV form (D = 128, GQA groups of 1/2/4/8)
-        self.attn_fq_ok = (torch.device(device).type == "cuda" and D == 128 and Hq % Hkv == 0
-                           and Hq // Hkv in (1, 2, 4, 8))
         self.moe_comm = "auto"
-        # decode fast path: skinny split-K GEMMs whose partial sums are reduced by
-        # the consuming kernel (rope_cache / add+rmsnorm); SiLU fused in gate_up.
-        Nqkv = (Hq + 2 * Hkv) * D
-        self.split_qkv = pick_split(Nqkv, H)
-        self.split_o = pick_split(H, Hq * D)
-        dims_ok = (H % 256 == 0 and (Hq * D) % 256 == 0 and Nqkv % 64 == 0 and H % 64 == 0
-                   and self.split_qkv and self.split_o)
-        if not self.moe:
-            Fl = cfg.intermediate_size // tp
-            self.split_down = pick_split(H, Fl)
-            dims_ok = dims_ok and Fl % 256 == 0 and (2 * Fl) % 64 == 0 and self.split_down
-        self.fast_ok = bool(dims_ok) and torch.device(device).type == "cuda"
-        # 16 < M <= 64: gemm_m64g for QKV / O / down (split-K partials into the consumers)
-        # and the fused SiLU-gate gate_up (measured: bench/gemm_bench.py)
-        self.m64_ok = self.fast_ok and all(
-            m64_plan(64, n, k, MODE_PARTIAL) is not None
-            for n, k in ((Nqkv, H), (H, Hq * D)) + (() if self.moe else ((H, cfg.intermediate_size // tp),)))
-        self.m64_silu_ok = self.m64_ok and not self.moe and m64_plan(64, 2 * (cfg.intermediate_size // tp), H,
-                                                                     MODE_SILU) is not None
-        # 64 < M <= MW_MAX_TOKENS: gemm_mw for every projection (MoE layers: the attention
-        # projections; the experts stay on the grouped gemm_m64g)
-        mw_shapes = ((Nqkv, H, MODE_PARTIAL), (H, Hq * D, MODE_PARTIAL))
-        if not self.moe:
-            mw_shapes += ((2 * (cfg.intermediate_size // tp), H, MODE_SILU),
-                          (H, cfg.intermediate_size // tp, MODE_PARTIAL))
-        self.mw_ok = self.fast_ok and MW_MAX_TOKENS > FAST_M_SLAB and all(
-            mw_plan(MW_MAX_TOKENS, n, k, mode) is not None and mw_plan(FAST_M_SLAB + 1, n, k, mode) is not None
-            for n, k, mode in mw_shapes)
-        # T > MW_MAX_TOKENS on TP = 1: gemm_pf for every projection (MoE layers: attention)
-        self.pf_ok = self.fast_ok and PF_MAX_M > 0 and tp == 1 and all(
-            pf_plan(PF_MAX_M, n, k, mode) is not None for n, k, mode in mw_shapes)
-        # M <= 16 too, when every projection has a measured small-M plan
         self.w8 = None  # fp8 / int8 / int4 weight copies for decode (LlamaForCausalLM.quantize_weights)
-        self.m64_small_ok = self.m64_ok and all(
-            m64_plan(1, n, k, MODE_PARTIAL) is not None
-            for n, k in ((Nqkv, H), (H, Hq * D)) + (() if self.moe else ((H, cfg.intermediate_size // tp),))) and (
-            self.moe or m64_plan(1, 2 * (cfg.intermediate_size // tp), H, MODE_SILU) is not None)
+        # the GEMM kernel of each projection and the attention entry, per step size
+        self.dispatch = d = LayerDispatch.for_layer(cfg, tp, torch.device(device).type == "cuda")
+        self.fast_ok, self.m64_small_ok, self.mw_ok, self.pf_ok, self.attn_fq_ok = (
+            d.fast_ok, d.m64_small_ok, d.mw_ok, d.pf_ok, d.attn_fq_ok)
 
-    def _w8_or_m64(self, x: torch.Tensor, name: str, mode: int):
-        """One projection of the fp8 decode chain: the E4M3 copy when the layer has
-        one, else the bf16 weight on gemm_m64g (same PendingSum / SiLU outputs)."""
-        q = self.w8.get(name)
-        if q is not None:
+    def _ar(self, x):
+        """Row-parallel output -> all-reduced tensor. TP = 1: as it is -- a PendingSum
+        goes on to its consumer's prologue. (Keyed on the layer's own TP degree: a TP=1
+        draft model may live in a TP>1 process.)"""
+        if self.tp == 1:
+            return x
+        return comm.tp_all_reduce(x.materialize() if isinstance(x, PendingSum) else x)
+
+    def _gemm(self, family: str, x: torch.Tensor, name: str, mode: int):
+        """Projection `name` of x on the kernel family a Step names (a missing kernel or
+        plan raises in the wrapper: no family stands in for another)."""
+        w = getattr(self, name)
+        if family == "lib":  # (the eager, host-bound steps first)
+            return F.linear(x, w)
+        if family == "pf":
+            return pf_linear(x, w, mode)
+        if family == "m64":
+            return m64_linear(x, w, mode)
+        if family == "mw":
+            return mw_linear(x, w, mode)
+        if family == "w8":
+            q = self.w8[name]
             return w8_linear(x, q[0], q[1], mode, fmt=q[2])
-        return m64_linear(x, getattr(self, name), mode)
-
-    def _ar(self, x: torch.Tensor) -> torch.Tensor:
-        # keyed on the layer's own TP degree: a TP=1 draft model may live in a TP>1 process
-        return x if self.tp == 1 else comm.tp_all_reduce(x)
+        assert family == "skinny", family
+        return skinny_linear(x, w, None, mode)
 
     # ------------------------------------------------------------------ MoE
     def _moe_allreduce(self, h: torch.Tensor) -> torch.Tensor:
@@ -317,21 +391,10 @@ class LlamaLayer(nn.Module):
         return not (h.shape[0] <= EP_AR_MAX_TOKENS and ar is not None and ar.can_run(h.contiguous()))
 
     def mlp(self, h: torch.Tensor) -> torch.Tensor:
-        if self.moe:
-            if self.tp > 1 and self._moe_use_alltoall(h):
-                return self._moe_alltoall(h)
-            return self._moe_allreduce(h)
-        gu = F.linear(h, self.gate_up)
-        a = ops.silu_and_mul(gu, interleave16=True)
-        if self.tp == 1 and splitk_prefill_ok(a, self.down):
-            return splitk_linear(a, self.down, linear_mod.SPLITK_PREFILL_S)  # reduced by the next add + norm
-        return self._ar(F.linear(a, self.down))
-
-    def _row_parallel_fast(self, a: torch.Tensor, w: torch.Tensor, split: int):
-        pend = skinny_linear(a, w, None, MODE_PARTIAL)
-        if self.tp == 1:
-            return pend  # reduced by the consumer's prologue
-        return self._ar(pend.materialize())
+        """The experts of a MoE layer (a dense layer's MLP is the tail of `forward`)."""
+        if self.tp > 1 and self._moe_use_alltoall(h):
+            return self._moe_alltoall(h)
+        return self._moe_allreduce(h)
 
     def forward(self, x, residual: Optional[torch.Tensor], meta: AttnMeta,
                 kv: Tuple[torch.Tensor, torch.Tensor], cos_sin: torch.Tensor):
@@ -342,103 +405,29 @@ class LlamaLayer(nn.Module):
         else:
             h, residual = ops.fused_add_rmsnorm(x, residual, self.input_norm, eps)
         T = meta.num_tokens
-        if self.w8 is not None and T <= W8_MAX_M:
-            # FP8 weights (gemm_w8): half the weight bytes of the bf16 decode chain; the
-            # split-K partials go to the same consumers (rope_cache / add+rmsnorm)
-            pqkv = self._w8_or_m64(h, "qkv", MODE_PARTIAL)
-            a = self.attn.from_partials(pqkv, meta, kv, cos_sin)
-            o = self._w8_or_m64(a, "o", MODE_PARTIAL)
-            if self.tp > 1:
-                o = self._ar(o.materialize())
-            h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-            act = self._w8_or_m64(h, "gate_up", MODE_SILU)
-            d = self._w8_or_m64(act, "down", MODE_PARTIAL)
-            return (d if self.tp == 1 else self._ar(d.materialize())), residual
-        if self.fast_ok and T <= FAST_M_SMALL and not self.m64_small_ok:
-            # M <= 16: every projection on the streaming skinny kernel (1.7x hipBLASLt
-            # on QKV/O at batch 1), split-K partials reduced by the consumers
-            pqkv = skinny_linear(h, self.qkv, None, MODE_PARTIAL)
-            a = self.attn.from_partials(pqkv, meta, kv, cos_sin)
-            o = self._row_parallel_fast(a, self.o, self.split_o)
-            h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-            if self.moe:
-                return self.mlp(h), residual
-            act = skinny_linear(h, self.gate_up, mode=MODE_SILU)
-            return self._row_parallel_fast(act, self.down, self.split_down), residual
-        if self.m64_ok and T <= FAST_M_SLAB:
-            # gemm_m64g (LDS-DMA weight streaming) for every projection: split-K partials
-            # go to the consumers (rope_cache / add+rmsnorm), SiLU-gate fused in gate_up;
-            # pure-decode steps reduce the QKV partials + RoPE + KV append in the
-            # attention prologue (one launch instead of two; MoE layers, TP fallback)
-            pqkv = m64_linear(h, self.qkv, MODE_PARTIAL)
-            if T == meta.num_decodes and self.attn_fq_ok:
-                a = self.attn.fused_decode(pqkv, meta, kv, cos_sin)
-            else:
-                a = self.attn.from_partials(pqkv, meta, kv, cos_sin)
-            o = m64_linear(a, self.o, MODE_PARTIAL)
-            if self.tp > 1:
-                o = self._ar(o.materialize())
-            h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-            if self.moe:
-                return self.mlp(h), residual
-            if self.m64_silu_ok:
-                act = m64_linear(h, self.gate_up, MODE_SILU)
-            else:
-                act = ops.silu_and_mul(F.linear(h, self.gate_up), interleave16=True)
-            d = m64_linear(act, self.down, MODE_PARTIAL)
-            return (d if self.tp == 1 else self._ar(d.materialize())), residual
-        if self.mw_ok and T <= MW_MAX_TOKENS:
-            # 64 < M <= 320 (decode rows + a prefill chunk): gemm_mw streams each weight
-            # once with the MFMA work under the stream; split-K partials go to the
-            # consumers (rope_cache_partials / add + rmsnorm), SiLU-gate in gate_up
-            pqkv = mw_linear(h, self.qkv, MODE_PARTIAL)
-            a = self.attn.from_partials(pqkv, meta, kv, cos_sin)
-            o = mw_linear(a, self.o, MODE_PARTIAL)
-            if self.tp > 1:
-                o = self._ar(o.materialize())
-            h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-            if self.moe:
-                return self.mlp(h), residual
-            act = mw_linear(h, self.gate_up, MODE_SILU)
-            d = mw_linear(act, self.down, MODE_PARTIAL)
-            return (d if self.tp == 1 else self._ar(d.materialize())), residual
-        use_pf = pf_projections(T) if self.pf_ok else frozenset()
-        if use_pf:
-            # prompt-sized mixed steps: gemm_pf for the projections whose measured window
-            # holds T (split-K partials into the consumers: rope_cache_partials / add +
-            # rmsnorm; the SiLU gate in the gate_up epilogue), the library GEMMs for the others
-            if "qkv" in use_pf:
-                a = self.attn.from_partials(pf_linear(h, self.qkv, MODE_PARTIAL), meta, kv, cos_sin)
-            else:
-                a = self.attn(F.linear(h, self.qkv), meta, kv, cos_sin)
-            o = pf_linear(a, self.o, MODE_PARTIAL) if "o" in use_pf else F.linear(a, self.o)
-            h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-            if self.moe:
-                return self.mlp(h), residual
-            if "gate_up" in use_pf:
-                act = pf_linear(h, self.gate_up, MODE_SILU)
-            else:
-                act = ops.silu_and_mul(F.linear(h, self.gate_up), interleave16=True)
-            if "down" in use_pf:
-                return pf_linear(act, self.down, MODE_PARTIAL), residual
-            if splitk_prefill_ok(act, self.down):
-                return splitk_linear(act, self.down, linear_mod.SPLITK_PREFILL_S), residual
-            return F.linear(act, self.down), residual
-        if self.fast_ok and T <= FAST_M_SLAB:
-            # 16 < M <= 64: measured per shape on MI355X -- only the O projection
-            # (N = H) is faster on the LDS-slab kernel; its split-K partials are
-            # reduced inside add+rmsnorm. QKV / gate_up / down stay on hipBLASLt.
-            qkv = F.linear(h, self.qkv)
+        step = self.dispatch.select(T, meta.num_decodes)
+        qkv = self._gemm(step.qkv, h, "qkv", MODE_PARTIAL)
+        if step.attn == "fused_decode":
+            a = self.attn.fused_decode(qkv, meta, kv, cos_sin)
+        elif step.attn == "from_partials":
+            a = self.attn.from_partials(qkv, meta, kv, cos_sin)
+        else:
             a = self.attn(qkv, meta, kv, cos_sin)
-            o = self._row_parallel_fast(a, self.o, self.split_o)
-            h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-            return self.mlp(h), residual
-        a = self.attn(F.linear(h, self.qkv), meta, kv, cos_sin)
-        if self.tp > 1 and not self.moe and T >= TP_OVERLAP_MIN_TOKENS and TP_OVERLAP_CHUNKS > 1:
+        if (self.tp > 1 and step is LIB and not self.moe and T >= TP_OVERLAP_MIN_TOKENS
+                and TP_OVERLAP_CHUNKS > 1):
             return self._forward_tp_overlap(a, residual)
-        o = self._ar(F.linear(a, self.o))
+        o = self._ar(self._gemm(step.o, a, "o", MODE_PARTIAL))
         h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
-        return self.mlp(h), residual
+        if self.moe:
+            return self.mlp(h), residual
+        if step.gate_up == "lib":
+            act = ops.silu_and_mul(F.linear(h, self.gate_up), interleave16=True)
+        else:
+            act = self._gemm(step.gate_up, h, "gate_up", MODE_SILU)
+        if step.down == "lib" and self.tp == 1 and splitk_prefill_ok(act, self.down):
+            # one K-split library GEMM, reduced by the next add + norm
+            return splitk_linear(act, self.down, linear_mod.SPLITK_PREFILL_S), residual
+        return self._ar(self._gemm(step.down, act, "down", MODE_PARTIAL)), residual
 
     def _forward_tp_overlap(self, a: torch.Tensor, residual: torch.Tensor):
         """Row-parallel half of a TP layer for prefill-sized steps, pipelined over
@@ -480,14 +469,14 @@ class LlamaLayer(nn.Module):
         (+ residual, + next statistics). `resid` (bf16 [T, H]) is updated in place;
         returns the statistics of the new residual for the next layer."""
         eps = self.cfg.norm_eps
-        pqkv = m64_norm_linear(resid, self.qkv, MODE_PARTIAL, stats, eps)
+        pqkv = m64_linear(resid, self.qkv, MODE_PARTIAL, stats=stats, eps=eps)
         a = self.attn.fused_decode(pqkv, meta, kv, cos_sin)
         if self.moe:
             return self._fused_moe_tail(a, resid, ws, site)
         if self.tp > 1:
             return self._fused_tp_tail(a, resid, ws, site)
         st = m64_resid_linear(a, self.o, resid, ws, site, eps)
-        act = m64_norm_linear(resid, self.gate_up, MODE_SILU, st, eps)
+        act = m64_linear(resid, self.gate_up, MODE_SILU, stats=st, eps=eps)
         return m64_resid_linear(act, self.down, resid, ws, site + 1, eps)
 
     def _fused_moe_tail(self, a, resid: torch.Tensor, ws: ResidWorkspace, site: int) -> RowStats:
@@ -527,12 +516,12 @@ class LlamaLayer(nn.Module):
         if ar is not None:
             # the all-reduce inside the O / down launches (gemm_m64g GG_AR): 2 launches fewer
             st = m64_ar_resid_linear(a, self.o, resid, ws, site, ar)
-            act = m64_norm_linear(resid, self.gate_up, MODE_SILU, st, eps)
+            act = m64_linear(resid, self.gate_up, MODE_SILU, stats=st, eps=eps)
             return m64_ar_resid_linear(act, self.down, resid, ws, site + 1, ar)
         po = m64_linear(a, self.o, MODE_PARTIAL)
         comm.tp_allreduce_resid(po.part, resid, ws.ss[site], self.tp)
         st = RowStats(ws.ss[site], H // 1024, T)
-        act = m64_norm_linear(resid, self.gate_up, MODE_SILU, st, eps)
+        act = m64_linear(resid, self.gate_up, MODE_SILU, stats=st, eps=eps)
         pd = m64_linear(act, self.down, MODE_PARTIAL)
         comm.tp_allreduce_resid(pd.part, resid, ws.ss[site + 1], self.tp)
         return RowStats(ws.ss[site + 1], H // 1024, T)
@@ -562,9 +551,7 @@ class LlamaForCausalLM(nn.Module):
         l0 = self.layers[0]
         self.norms_folded = False
         self.weight_dtype = "bf16"
-        self._fused_ok = (self.device.type == "cuda" and l0.m64_ok and (l0.moe or l0.m64_silu_ok)
-                          and cfg.head_dim == 128 and l0.Hq % l0.Hkv == 0
-                          and l0.Hq // l0.Hkv in (1, 2, 4, 8) and H % 1024 == 0 and H // 1024 <= 8)
+        self._fused_ok = l0.fast_ok and l0.attn_fq_ok and H % 1024 == 0 and H // 1024 <= 8
         self._fused_small_ok = self._fused_ok and l0.m64_small_ok
         # every layer on gemm_mw for 64 < T <= MW_MAX_TOKENS (the runner's mixed-step graphs)
         self._mw_ok = self.device.type == "cuda" and all(l.mw_ok for l in self.layers)
@@ -614,6 +601,7 @@ class LlamaForCausalLM(nn.Module):
         chosen = [n for n in names if use_q(n)]
         for l in self.layers:
             l.w8 = {n: quantize_weight(getattr(l, n), fmt) + (fmt,) for n in chosen}
+            l.dispatch.set_quantized(chosen)
         self._fused_ok = self._fused_small_ok = False
         self.weight_dtype = kind
         return True

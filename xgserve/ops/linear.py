@@ -1,4 +1,8 @@
-"""Decode-regime projections on the skinny HIP GEMM (csrc/kernels/skinny_gemm.hip).
+"""The projections' HIP GEMMs, one wrapper and one planner per kernel: skinny_gemm
+(M <= 16 register streaming), gemm_m64g (M <= 64, with the fused decode layer's
+row-scale / residual / all-reduce epilogues), gemm_mw (64 < M <= 320), gemm_pf
+(prompt-sized M), gemm_w8 (fp8 / int8 / int4 weights, M <= 64), and the split-K
+library GEMM for prefill-sized down projections.
 
 `PendingSum` is a value that exists only as fp32 split-K partial sums; the
 kernels that consume it (add_partials_rmsnorm, rope_cache_partials) reduce it
@@ -34,6 +38,18 @@ class PendingSum:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=self.part.device)
         kernels().reduce_partials(self.part.data_ptr(), S, M * N, out.data_ptr(), stream_ptr())
         return out
+
+
+def _result(x: torch.Tensor, M: int, N: int, S: int, mode: int, out: Optional[torch.Tensor] = None):
+    """What a GEMM wrapper returns, with the kernel's (partials, output) pointers, one of
+    them 0: a PendingSum of S fp32 slabs [S, M, N] (MODE_PARTIAL), else `out` or a new
+    bf16 [M, N] (MODE_BF16) / [M, N / 2] (MODE_SILU)."""
+    if mode == MODE_PARTIAL:
+        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
+        return PendingSum(part, S), part.data_ptr(), 0
+    if out is None:
+        out = torch.empty(M, N // 2 if mode == MODE_SILU else N, dtype=torch.bfloat16, device=x.device)
+    return out, 0, out.data_ptr()
 
 
 def pick_split(N: int, K: int, target_wgs: int = 512) -> int:
@@ -72,16 +88,10 @@ def skinny_linear(x: torch.Tensor, w: torch.Tensor, split_k: Optional[int] = Non
     or silu(gate)*up [M, N/2] for a block-16 interleaved gate|up weight (MODE_SILU)."""
     M, K = x.shape
     N = w.shape[0]
-    if mode == MODE_PARTIAL:
-        S = split_k or choose_split(M, N, K)
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        kernels().skinny_gemm(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), 0, S, MODE_PARTIAL, stream_ptr())
-        return PendingSum(part, S)
-    ncol = N // 2 if mode == MODE_SILU else N
-    if out is None:
-        out = torch.empty(M, ncol, dtype=torch.bfloat16, device=x.device)
-    kernels().skinny_gemm(x.data_ptr(), M, K, w.data_ptr(), N, 0, out.data_ptr(), 1, mode, stream_ptr())
-    return out
+    S = (split_k or choose_split(M, N, K)) if mode == MODE_PARTIAL else 1
+    res, part, outp = _result(x, M, N, S, mode, out)
+    kernels().skinny_gemm(x.data_ptr(), M, K, w.data_ptr(), N, part, outp, S, mode, stream_ptr())
+    return res
 
 
 # gemm_m64g launch configurations (csrc/kernels/gemm_m64g.hip launch_m64g):
@@ -199,10 +209,13 @@ def m64_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL):
 
 
 def m64_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, split_k: Optional[int] = None,
-               nw: Optional[int] = None, out: Optional[torch.Tensor] = None, cfg: Optional[int] = None):
+               nw: Optional[int] = None, out: Optional[torch.Tensor] = None, cfg: Optional[int] = None,
+               stats: Optional[RowStats] = None, eps: float = 0.0):
     """gemm_m64g (csrc/kernels/gemm_m64g.hip, LDS-DMA weight streaming) for M <= 64:
     bf16 [M, N], PendingSum (MODE_PARTIAL) or silu(gate)*up [M, N/2] (MODE_SILU,
-    interleaved gate|up weight)."""
+    interleaved gate|up weight). With `stats`, x is the raw residual stream and its
+    RMSNorm is applied as a per-row epilogue scale rsqrt(sum_sq / K + eps) (the norm
+    weight folded into w)."""
     M, K = x.shape
     N = w.shape[0]
     plan = m64_plan(M, N, K, mode)
@@ -219,21 +232,20 @@ def m64_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, split
         cfg = plan[2] if cfg is None else cfg
         if not _m64_valid(N, K, mode, nw, S, cfg, M):
             cfg = 0
-    k = kernels()
-    if mode == MODE_PARTIAL:
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        k.gemm_m64g(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), 0, S, MODE_PARTIAL, nw, cfg, stream_ptr())
-        return PendingSum(part, S)
-    ncol = N // 2 if mode == MODE_SILU else N
-    if out is None:
-        out = torch.empty(M, ncol, dtype=torch.bfloat16, device=x.device)
+    res, part, outp = _result(x, M, N, S, mode, out)
+    tickets = 0
     if mode == MODE_SILU and S > 1:  # split-K SiLU: slabs + tile tickets, reduced in the GEMM tail
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        k.gemm_m64g_ex(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), out.data_ptr(), S, mode, nw, cfg,
-                       0, 0, 0, 0.0, 0, 0, tile_counters(x.device, N).data_ptr(), stream_ptr())
+        slabs = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
+        part, tickets = slabs.data_ptr(), tile_counters(x.device, N).data_ptr()
+    elif mode != MODE_PARTIAL:
+        S = 1
+    if stats is None and not tickets:
+        kernels().gemm_m64g(x.data_ptr(), M, K, w.data_ptr(), N, part, outp, S, mode, nw, cfg, stream_ptr())
     else:
-        k.gemm_m64g(x.data_ptr(), M, K, w.data_ptr(), N, 0, out.data_ptr(), 1, mode, nw, cfg, stream_ptr())
-    return out
+        st = (0, 0, 0, 0.0) if stats is None else (stats.ss.data_ptr(), stats.n, stats.stride, float(eps))
+        kernels().gemm_m64g_ex(x.data_ptr(), M, K, w.data_ptr(), N, part, outp, S, mode, nw, cfg, *st, 0, 0, tickets,
+                               stream_ptr())
+    return res
 
 
 # ---------------------------------------------------------------------------- gemm_mw (64 < M <= 256)
@@ -291,15 +303,9 @@ def mw_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, plan=N
     if p is None or not x.is_contiguous():
         raise ValueError(f"gemm_mw: unsupported M={M} N={N} K={K} mode={mode}")
     S, cfg = p
-    if mode == MODE_PARTIAL:
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        kernels().gemm_mw(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), 0, S, MODE_PARTIAL, cfg,
-                          stream_ptr())
-        return PendingSum(part, S)
-    if out is None:
-        out = torch.empty(M, N // 2 if mode == MODE_SILU else N, dtype=torch.bfloat16, device=x.device)
-    kernels().gemm_mw(x.data_ptr(), M, K, w.data_ptr(), N, 0, out.data_ptr(), S, mode, cfg, stream_ptr())
-    return out
+    res, part, outp = _result(x, M, N, S, mode, out)
+    kernels().gemm_mw(x.data_ptr(), M, K, w.data_ptr(), N, part, outp, S, mode, cfg, stream_ptr())
+    return res
 
 
 # ---------------------------------------------------------------------------- gemm_pf (prompt-sized M)
@@ -377,15 +383,9 @@ def pf_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_BF16, plan=None
     if p is None or not x.is_contiguous() or not w.is_contiguous():
         raise ValueError(f"gemm_pf: unsupported M={M} N={N} K={K} mode={mode}")
     S, cfg = p[0], p[1]
-    k = kernels()
-    if mode == MODE_PARTIAL:
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        k.gemm_pf(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), 0, S, MODE_PARTIAL, cfg, stream_ptr())
-        return PendingSum(part, S)
-    if out is None:
-        out = torch.empty(M, N // 2 if mode == MODE_SILU else N, dtype=torch.bfloat16, device=x.device)
-    k.gemm_pf(x.data_ptr(), M, K, w.data_ptr(), N, 0, out.data_ptr(), S, mode, cfg, stream_ptr())
-    return out
+    res, part, outp = _result(x, M, N, S, mode, out)
+    kernels().gemm_pf(x.data_ptr(), M, K, w.data_ptr(), N, part, outp, S, mode, cfg, stream_ptr())
+    return res
 
 
 def lm_head_linear(h: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -519,35 +519,9 @@ def tile_counters(device, n: int) -> torch.Tensor:
     return t
 
 
-def m64_norm_linear(x: torch.Tensor, w: torch.Tensor, mode: int, stats: RowStats, eps: float,
-                    out: Optional[torch.Tensor] = None, plan=None):
-    """gemm_m64g on the raw residual stream x with its RMSNorm applied as a per-row
-    epilogue scale rsqrt(sum_sq / K + eps) (norm weight folded into w): PendingSum
-    (MODE_PARTIAL) or bf16 silu(gate) * up (MODE_SILU). plan: (nw, S, cfg) override
-    (sweeps)."""
-    M, K = x.shape
-    N = w.shape[0]
-    plan = plan or m64_plan(M, N, K, mode)
-    if plan is None:
-        raise ValueError(f"gemm_m64g: unsupported shape M={M} N={N} K={K} mode={mode}")
-    nw, S, cfg = plan
-    k = kernels()
-    st = (stats.ss.data_ptr(), stats.n, stats.stride, float(eps))
-    if mode == MODE_PARTIAL:
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        k.gemm_m64g_ex(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), 0, S, MODE_PARTIAL, nw, cfg, *st,
-                       0, 0, 0, stream_ptr())
-        return PendingSum(part, S)
-    if out is None:
-        out = torch.empty(M, N // 2 if mode == MODE_SILU else N, dtype=torch.bfloat16, device=x.device)
-    if mode == MODE_SILU and S > 1:  # split-K SiLU: slabs + tile tickets, reduced in the GEMM tail
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        k.gemm_m64g_ex(x.data_ptr(), M, K, w.data_ptr(), N, part.data_ptr(), out.data_ptr(), S, mode, nw, cfg, *st,
-                       0, 0, tile_counters(x.device, N).data_ptr(), stream_ptr())
-        return out
-    k.gemm_m64g_ex(x.data_ptr(), M, K, w.data_ptr(), N, 0, out.data_ptr(), 1, mode, nw, cfg, *st, 0, 0, 0,
-                   stream_ptr())
-    return out
+def m64_norm_linear(x, w, mode, stats: RowStats, eps: float, out=None):
+    """The earlier name of m64_linear(..., stats=, eps=), kept for its callers outside this tree."""
+    return m64_linear(x, w, mode, out=out, stats=stats, eps=eps)
 
 
 def m64_resid_linear(x, w: torch.Tensor, resid: torch.Tensor, ws: ResidWorkspace, site: int,
@@ -772,17 +746,11 @@ def w8_linear(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, mode: int =
     p = plan or w8_plan(M, N, K, mode, fmt)
     kq = K // 2 if fmt == WQ_INT4 else K
     if (p is None or not x.is_contiguous() or q.dtype != torch.uint8 or scale.dtype != torch.float32
+            or mode not in (MODE_PARTIAL, MODE_SILU)
             or tuple(q.shape) != (N, kq) or scale.numel() != (N * (K // WQ_GROUP) if fmt == WQ_INT4 else N)):
         raise ValueError(f"gemm_w8: unsupported M={M} N={N} K={K} mode={mode} fmt={fmt}")
-    S, cfg = p
-    k = kernels()
-    if mode == MODE_PARTIAL:
-        part = torch.empty(S, M, N, dtype=torch.float32, device=x.device)
-        k.gemm_w8(x.data_ptr(), M, K, q.data_ptr(), scale.data_ptr(), N, part.data_ptr(), 0, S, MODE_PARTIAL, cfg,
-                  stream_ptr(), fmt)
-        return PendingSum(part, S)
-    if out is None:
-        out = torch.empty(M, N // 2, dtype=torch.bfloat16, device=x.device)
-    k.gemm_w8(x.data_ptr(), M, K, q.data_ptr(), scale.data_ptr(), N, 0, out.data_ptr(), 1, MODE_SILU, cfg,
-              stream_ptr(), fmt)
-    return out
+    S, cfg = p[0] if mode == MODE_PARTIAL else 1, p[1]
+    res, part, outp = _result(x, M, N, S, mode, out)
+    kernels().gemm_w8(x.data_ptr(), M, K, q.data_ptr(), scale.data_ptr(), N, part, outp, S, mode, cfg, stream_ptr(),
+                      fmt)
+    return res
