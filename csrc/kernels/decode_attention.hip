@@ -16,6 +16,14 @@
 // Waves stride over tiles; the 4 wave states (m, l, O) merge through LDS at the
 // end. With S > 1 each split writes (O/l, lse) and decode_combine reduces.
 //
+// Guarantee (as in prefill): cache rows past a sequence's end never reach the
+// output, whatever they hold -- pages are recycled without clearing, so they may
+// hold another request's NaN / Inf. The last 16-key tile is loaded whole: scores
+// of keys >= L are replaced by -inf (a NaN key row dies in that select), and the V
+// loads of rows >= L are clamped to row L - 1, since a probability of exactly 0
+// does not protect the MFMA from 0 * Inf. Every form: K through LDS or not, fused
+// or not.
+//
 // Fused-QKV form (FQ; the dense decode layer, see gemm_m64g.hip): the QKV
 // projection arrives as fp32 split-K partials. Each workgroup's prologue reduces
 // the partials of ITS (sequence, kv head) -- the G query heads plus the k and v
@@ -356,6 +364,11 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(
     // K/V are read once per step and a step's cache (GBs at 64 sequences) never fits the
     // L2 / Infinity Cache: non-temporal loads, 5.3 -> 6.1 TB/s at 2K keys (r4_decode_nt.md)
     auto ldkv = [](const uint16_t* p) { return PR == 4 ? ld16(p) : ld16_nt(p); };
+    // V rows past the sequence's end re-read its last row (address arithmetic, no
+    // branch around the loads): their probability is exactly 0, but 0 * Inf and
+    // 0 * NaN on the MFMA are NaN, and a recycled page may hold anything there.
+    // K needs no clamp: the scores of those keys are replaced by -inf, never used.
+    const int vmax = t < 0 ? 15 : L - 1 - key0;  // >= 15 on every tile but a sequence's last
     if constexpr (KL) {
       static_assert(C::KK == C::VLD, "K and V tiles split into the same chunks per lane");
 #pragma unroll
@@ -371,7 +384,7 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(
 #pragma unroll
     for (int i = 0; i < C::VLD; ++i) {
       const int c = lane + 64 * i;  // chunk id in the 16 x NCH tile
-      vr[i] = ldkv(vc + base + (c / C::NCH) * D + (c % C::NCH) * 8);
+      vr[i] = ldkv(vc + base + min(c / C::NCH, vmax) * D + (c % C::NCH) * 8);
     }
   };
   const int t0 = t_begin + wid;

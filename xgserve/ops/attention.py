@@ -89,7 +89,10 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                      seq_lens: torch.Tensor, scale: float, num_splits: int = 1,
                      workspace: Optional[DecodeWorkspace] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q: [B, Hq, D] (rows may be strided, e.g. a view into the QKV buffer).
-    k/v_cache: [NB, Hkv, bs, D]; block_tables [B, W] int32; seq_lens [B] int32."""
+    k/v_cache: [NB, Hkv, bs, D]; block_tables [B, W] int32; seq_lens [B] int32.
+    Only rows < seq_lens[b] of a sequence's pages reach the output: rows past its end
+    (recycled pages are not cleared) may hold anything, NaN and Inf included. The same
+    holds for decode_attention_fused. A row with seq_lens[b] == 0 gives exactly 0."""
     if not use_native(q):
         r = decode_attention_ref(q, k_cache, v_cache, block_tables, seq_lens, scale)
         if out is not None:
