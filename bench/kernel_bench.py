@@ -167,11 +167,42 @@ def bench_moe_route(res, H=4096, E=8, k=2, layers=32):
     res.append({"op": "rmsnorm (launch floor)", "T": 1, "us_graph": round(graphed(lambda: ops.rmsnorm(resid, nw, 1e-5)), 2)})
 
 
+def bench_dequant(res, N, K, kind):
+    """dequant_w8 (quantized weight -> the bf16 scratch of a quantized-only model), device
+    time per call from a HIP graph of launches that rotate over enough weight copies to
+    exceed the 256 MiB Infinity Cache (a model's weights are cold at every step), all
+    writing the one scratch. GB/s counts code + scale bytes read plus bf16 bytes written."""
+    from xgserve.ops.linear import WQ_FORMATS, dequantize_into, quantize_weight
+    dev = "cuda"
+    fmt = WQ_FORMATS[kind]
+    q, s = quantize_weight(torch.randn(N, K, device=dev) * 0.02, fmt)
+    rd = q.numel() + 4 * s.numel()
+    copies = [(q, s)] + [(q.clone(), s.clone()) for _ in range(max(1, (512 << 20) // rd))]
+    out = torch.empty(N * K, dtype=torch.bfloat16, device=dev)
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        dequantize_into(q, s, fmt, out=out)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=st):
+            for cq, cs in copies:
+                dequantize_into(cq, cs, fmt, out=out)
+    torch.cuda.synchronize()
+    us = timeit(g.replay, iters=10, warm=2) / len(copies)
+    res.append({"op": "dequant_w8", "fmt": kind, "N": N, "K": K, "us_graph": round(us, 2),
+                "GB/s": round((rd + 2 * N * K) / us / 1e3, 1)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="all")
     a = ap.parse_args()
     res = []
+    if a.what in ("all", "dequant"):
+        # the four Llama-3-8B projections and the 70B gate_up
+        for (N, K) in ((6144, 4096), (4096, 4096), (28672, 4096), (4096, 14336), (57344, 8192)):
+            for kind in ("fp8", "int8", "int4"):
+                bench_dequant(res, N, K, kind)
     if a.what in ("all", "decode"):
         bench_decode(res, 64, 800, [1, 2, 4])
         bench_decode(res, 1, 1024, [1, 8, 16, 32])

@@ -4,7 +4,10 @@
 (32 q / 8 kv heads) and Llama-3-70B (64 / 8) head layouts, every GQA head-group
 width `gh` (query heads per workgroup). TFLOP/s counts the causal work:
 4 * Hq * D * L (L + 1) / 2. Also --ttft: end-to-end batch-1 TTFT of one
---ttft-len-token prompt through the engine (random-init Llama-3-8B, bf16)."""
+--ttft-len-token prompt through the engine (random-init Llama-3-8B, bf16, or
+--quantization fp8|int8|int4 with or without --quantized-only; --ttft-only skips the
+attention sweep), followed by the tok/s of --batch prompts of --batch-prompt-len
+tokens generating --batch-out tokens each (prompt steps and decode steps together)."""
 import argparse
 import json
 import math
@@ -44,10 +47,13 @@ def bench_attn(L, Hq, Hkv, D, gh, iters=20, bs=16):
     return us, flops / us / 1e6
 
 
-def ttft(L):
+def ttft(L, quantization=None, quantized_only=False, batch=0, batch_prompt_len=512, batch_out=64):
     from xgserve.engine import EngineConfig, LLMEngine, SamplingParams
-    eng = LLMEngine(EngineConfig(model="llama3-8b", max_num_seqs=4, max_num_batched_tokens=max(8192, L),
-                                 max_model_len=L + 16, graph_batch_sizes=[1]))
+    wdt = quantization if quantization in ("fp8", "int8", "int4") else None
+    bs = sorted({1, *(b for b in (2, 4, 8, 16, 32, 64) if b <= batch)})
+    eng = LLMEngine(EngineConfig(model="llama3-8b", max_num_seqs=max(4, batch), max_num_batched_tokens=max(8192, L),
+                                 max_model_len=max(L, batch_prompt_len + batch_out) + 16, graph_batch_sizes=bs,
+                                 weight_dtype=wdt, quantized_only=quantized_only))
     res = []
     for it in range(4):
         prompt = torch.randint(10, 128000, (L,)).tolist()
@@ -61,7 +67,21 @@ def ttft(L):
                     done = True
         res.append(1000 * (time.perf_counter() - t0))
         eng.clear_prefix_cache()
-    return res
+    extra = dict(eng.stats())
+    extra = {k: extra[k] for k in ("weight_bytes", "scratch_bytes", "weight_dtype", "kv_blocks_total")}
+    if batch > 0:
+        sp = SamplingParams(max_tokens=batch_out, temperature=0.0, ignore_eos=True)
+        for it in range(2):  # the second run is the measured one
+            prompts = [torch.randint(10, 128000, (batch_prompt_len,)).tolist() for _ in range(batch)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = eng.generate(prompts, sp)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            eng.clear_prefix_cache()
+        extra.update(batch=batch, batch_prompt_len=batch_prompt_len, batch_out=batch_out,
+                     batch_s=round(dt, 4), output_tok_s=round(sum(len(o) for o in outs) / dt, 1))
+    return res, extra
 
 
 def main():
@@ -70,19 +90,27 @@ def main():
     ap.add_argument("--gh", type=int, nargs="+", default=[0, 4, -44, -84, -82, -1284, -1282, -1281])
     ap.add_argument("--ttft-len", type=int, default=8000)
     ap.add_argument("--no-ttft", action="store_true")
+    ap.add_argument("--ttft-only", action="store_true", help="skip the attention sweep")
+    ap.add_argument("--quantization", default="bf16", choices=["bf16", "fp8", "int8", "int4"])
+    ap.add_argument("--quantized-only", action="store_true",
+                    help="release the bf16 projection weights (prompt steps dequantize into a scratch)")
+    ap.add_argument("--batch", type=int, default=0, help="also time this many prompts generating together")
+    ap.add_argument("--batch-prompt-len", type=int, default=512)
+    ap.add_argument("--batch-out", type=int, default=64)
     a = ap.parse_args()
     kernels()
     for name, Hq, Hkv in (("llama3-8b", 32, 8), ("llama3-70b", 64, 8)):
-        for L in a.lens:
+        for L in ([] if a.ttft_only else a.lens):
             for gh in a.gh:
                 us, tf = bench_attn(L, Hq, Hkv, 128, gh)
                 print(json.dumps({"op": "prefill_attention", "heads": name, "L": L, "gh": gh, "us": round(us, 1),
                                   "TFLOP/s": round(tf, 1)}), flush=True)
     if not a.no_ttft:
-        r = ttft(a.ttft_len)
+        r, extra = ttft(a.ttft_len, a.quantization, a.quantized_only, a.batch, a.batch_prompt_len, a.batch_out)
         print(json.dumps({"op": "ttft_batch1", "model": "llama3-8b", "prompt_len": a.ttft_len,
-                          "ttft_ms": [round(x, 2) for x in r], "ttft_ms_best_of_last3": round(min(r[1:]), 2)}),
-              flush=True)
+                          "quantization": a.quantization, "quantized_only": a.quantized_only,
+                          "ttft_ms": [round(x, 2) for x in r], "ttft_ms_best_of_last3": round(min(r[1:]), 2),
+                          **extra}), flush=True)
 
 
 if __name__ == "__main__":

@@ -72,6 +72,7 @@ void segment_sum(const uint16_t*, int, const int32_t*, const int32_t*, float*, i
 void subst_tokens(int32_t*, const int32_t*, const int32_t*, int, hipStream_t);
 int gemm_w8(const uint16_t*, int, int, const uint8_t*, const float*, int, float*, uint16_t*, int, int, int,
             hipStream_t, int);
+int dequant_w8(const uint8_t*, const float*, int, int, uint16_t*, int, hipStream_t);
 void moe_topk_softmax(const void*, int, int, int, int, int, float*, int32_t*, hipStream_t);
 void moe_align(const int32_t*, int, int, int, int, int, int32_t*, int32_t*, int32_t*, hipStream_t);
 int moe_combine(const void*, int, int, const int32_t*, const float*, void*, int, int, int, hipStream_t, int);
@@ -232,6 +233,10 @@ PYBIND11_MODULE(_kernels, m) {
           "gemm_w8");
   }, py::arg("x"), py::arg("M"), py::arg("K"), py::arg("w"), py::arg("scale"), py::arg("N"), py::arg("part"),
      py::arg("out"), py::arg("splits"), py::arg("mode"), py::arg("cfg"), py::arg("st"), py::arg("fmt") = 0);
+  m.def("dequant_w8", [](uintptr_t q, uintptr_t scale, int N, int K, uintptr_t out, int fmt, uintptr_t st) {
+    check(xgk::dequant_w8(P<const uint8_t>(q), P<const float>(scale), N, K, P<uint16_t>(out), fmt, S(st)),
+          "dequant_w8");
+  }, py::arg("q"), py::arg("scale"), py::arg("N"), py::arg("K"), py::arg("out"), py::arg("fmt"), py::arg("st"));
   m.def("subst_tokens", [](uintptr_t ids, uintptr_t src, uintptr_t prev, int n, uintptr_t st) {
     xgk::subst_tokens(P<int32_t>(ids), P<const int32_t>(src), P<const int32_t>(prev), n, S(st));
     check(0, "subst_tokens");

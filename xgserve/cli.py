@@ -33,6 +33,8 @@ def _common(p: argparse.ArgumentParser) -> None:
     p.add_argument("--device", help="force a device, e.g. cpu")
     p.add_argument("--quantization", choices=["bf16", "fp16", "fp32", "fp8", "int8", "int4"],
                    help="fp8: E4M3 weights (per-channel scales) for batch <= 16 decode, bf16 activations")
+    p.add_argument("--quantized-only", action="store_true", default=None,
+                   help="with fp8|int8|int4: release the bf16 projection weights and serve from the quantized ones alone")
     p.add_argument("--strategy", choices=["round_robin", "least_loaded", "memory_aware"])
     p.add_argument("--batch-mode", choices=["continuous", "static"])
     p.add_argument("--max-num-seqs", type=int)
@@ -50,7 +52,8 @@ def _overrides(a) -> dict:
     return {
         "api": {"host": a.host, "port": a.port, "frontends": getattr(a, "frontends", None)},
         "worker": {"model": a.model, "checkpoint": a.checkpoint, "tp": a.tp, "replicas": a.replicas, "gpus": a.gpus,
-                   "device": a.device, "quantization": a.quantization, "max_num_seqs": a.max_num_seqs,
+                   "device": a.device, "quantization": a.quantization, "quantized_only": a.quantized_only,
+                   "max_num_seqs": a.max_num_seqs,
                    "max_model_len": a.max_model_len, "mock": a.mock, "in_process": a.in_process,
                    "use_graphs": (False if a.no_graphs else None),
                    "random_init": (False if a.checkpoint else None)},

@@ -99,6 +99,10 @@ class EngineConfig:
     early_release: bool = True
     # "fp8": weight-only E4M3 copies for batch <= 16 decode (bf16 activations)
     weight_dtype: Optional[str] = None
+    # serve from the fp8 / int8 / int4 weights alone: the bf16 projection weights are
+    # released (their bytes go to the KV pool) and steps above 64 rows dequantize one
+    # projection at a time into a shared scratch (LlamaForCausalLM.quantize_weights)
+    quantized_only: bool = False
     # custom xGMI all-reduce peer-wait limit while serving: a TP peer this late fails
     # the step (CustomAllReduceTimeout -> replica restart); warmup runs under 20 s
     collective_timeout_s: float = 2.0
@@ -126,8 +130,14 @@ class LLMEngine:
         t0 = time.time()
         self.model = model if model is not None else build_model(self.mcfg, device=device, dtype=dtype,
                                                                  checkpoint=cfg.checkpoint, seed=cfg.seed,
-                                                                 weight_dtype=cfg.weight_dtype)
+                                                                 weight_dtype=cfg.weight_dtype,
+                                                                 quantized_only=cfg.quantized_only)
         self.model.set_moe_comm(cfg.moe_comm)
+        # static after load: resident weight bytes (parameters + quantized copies) and the
+        # quantized-only dequantization scratch, reported by stats()
+        self._weight_bytes = int(self.model.weight_bytes()) if hasattr(self.model, "weight_bytes") else \
+            sum(p.numel() * p.element_size() for p in self.model.parameters())
+        self._scratch_bytes = int(self.model.scratch_bytes()) if hasattr(self.model, "scratch_bytes") else 0
         self.load_time = time.time() - t0
         from ..parallel.custom_ar import maybe_enable
         m = self.mcfg
@@ -773,6 +783,9 @@ class LLMEngine:
             "memory_used": self.sched.num_used_blocks() * bb,
             "memory_available": (self.sched.num_free_blocks() + self.sched.num_evictable_blocks()) * bb,
             "memory_limit": int(self.sched.num_blocks() * bb * self.cfg.cache_threshold),
+            "weight_bytes": self._weight_bytes,
+            "scratch_bytes": self._scratch_bytes,
+            "weight_dtype": getattr(self.model, "weight_dtype", None) or str(self.model.dtype).replace("torch.", ""),
             "cache": cs,
             "preemptions": self.sched.total_preemptions(),
             **self.stats_counters,

@@ -161,6 +161,7 @@ class MockEngine:
                 "kv_blocks_used": used, "kv_blocks_free": self.num_blocks - used, "kv_usage": self.kv_usage(),
                 "memory_used": used * 1024, "memory_available": (self.num_blocks - used) * 1024,
                 "memory_limit": int(self.num_blocks * 1024 * 0.8),
+                "weight_bytes": 0, "scratch_bytes": 0, "weight_dtype": "mock",
                 "cache": {"entries": 0, "hit_tokens": 0, "miss_tokens": 0, "hit_count": 0, "miss_count": 0,
                           "eviction_count": 0},
                 "preemptions": 0, **self.stats_counters}

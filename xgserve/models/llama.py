@@ -23,6 +23,9 @@ add + RMSNorm -> gate_up GEMM with the SiLU gate -> down GEMM (-> AR). LayerDisp
 picks each projection's GEMM kernel from the step size: gemm_w8 (quantized copies)
 or gemm_m64g up to 64 tokens (skinny_gemm up to 16 where gemm_m64g has no small-M
 plan), gemm_mw up to 320, gemm_pf inside its measured windows, else the library.
+A quantized-only model (quantize_weights(kind, quantized_only=True)) has no bf16
+projection weights: above 64 tokens each projection is dequantized (dequant.hip)
+into one shared bf16 scratch that the library GEMM reads.
 The HIP GEMMs hand split-K partials to their consumer (the attention prologue or
 add + RMSNorm) and gate inside gate_up; the library GEMMs are followed by rope_cache
 and silu_and_mul launches. Pure-decode steps of dense and MoE models normally take
@@ -42,9 +45,9 @@ from .. import ops, tune
 from ..parallel import comm
 from ..parallel.state import get_state
 from ..ops import linear as linear_mod
-from ..ops.linear import (MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M, W8_MIN_ELEMS, PendingSum, ResidWorkspace,
-                          RowStats, lm_head_linear, m64_ar_resid_linear, m64_linear, m64_plan,
-                          m64_resid_linear,
+from ..ops.linear import (MODE_BF16, MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M, W8_MIN_ELEMS, PendingSum,
+                          ResidWorkspace, RowStats, dequantize_into, lm_head_linear, m64_ar_resid_linear,
+                          m64_linear, m64_plan, m64_resid_linear,
                           mw_linear, mw_plan, pf_linear, pf_plan,
                           quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
                           w8_plan, WQ_FORMATS)
@@ -132,7 +135,8 @@ PROJECTIONS = ("qkv", "o", "gate_up", "down")
 class Step(NamedTuple):
     """The GEMM kernel family of each projection at one step -- "w8", "skinny", "m64",
     "mw", "pf" (HIP: QKV / O / down as split-K partials into their consumers, the SiLU
-    gate inside gate_up) or "lib" (library GEMM, bf16 out) -- and the attention entry:
+    gate inside gate_up), "lib" (library GEMM, bf16 out) or "dq" (the quantized weight
+    dequantized into the model's scratch, then the library GEMM) -- and the attention entry:
     "fused_decode" / "from_partials" for QKV partials, "rope" for a QKV tensor. MoE
     layers run their experts (LlamaLayer.mlp) in place of gate_up / down."""
     qkv: str
@@ -171,6 +175,7 @@ class LayerDispatch:
     def __init__(self, Nqkv: int, H: int, HqD: int, Fl: int, moe: bool, tp: int, on_gpu: bool, attn_fq_ok: bool):
         self.attn_fq_ok = attn_fq_ok    # the decode attention kernel's fused-QKV form fits the head layout
         self.quantized: Optional[Step] = None
+        self.dequantized: Optional[Step] = None  # T > W8_MAX_M of a model without its bf16 weights
         self.fast_ok = on_gpu and H % 256 == 0 and HqD % 256 == 0 and Nqkv % 64 == 0 and (moe or Fl % 256 == 0)
         shapes = ((Nqkv, H, MODE_PARTIAL), (H, HqD, MODE_PARTIAL))
         if not moe:
@@ -195,14 +200,20 @@ class LayerDispatch:
         return cls((Hq + 2 * Hkv) * D, cfg.hidden_size, Hq * D, 0 if moe else cfg.intermediate_size // tp, moe, tp,
                    on_gpu, attn_fq_ok)
 
-    def set_quantized(self, names) -> None:
+    def set_quantized(self, names, resident: bool = True) -> None:
         """The projections in `names` have fp8 / int8 / int4 copies (gemm_w8, T <= W8_MAX_M);
-        the others run their bf16 weight on gemm_m64g there."""
+        the others run their bf16 weight on gemm_m64g there. resident=False: the bf16
+        weights of `names` are gone, so every larger step dequantizes them into the
+        model's scratch for the library GEMM ("dq") -- no bf16 HIP GEMM family is ever
+        chosen for them."""
         self.quantized = Step(*("w8" if n in names else "m64" for n in PROJECTIONS), "from_partials")
+        self.dequantized = None if resident else Step(*("dq" if n in names else "lib" for n in PROJECTIONS), "rope")
 
     def select(self, T: int, num_decodes: int) -> Step:
         if self.quantized is not None and T <= W8_MAX_M:
             return self.quantized
+        if self.dequantized is not None:
+            return self.dequantized
         if self.fast_ok and T <= FAST_M_SLAB:
             if T <= FAST_M_SMALL and not self.m64_small_ok:
                 return SKINNY
@@ -257,6 +268,10 @@ class LlamaLayer(nn.Module):
         self.attn = PagedAttention(Hq, Hkv, D)
         self.moe_comm = "auto"
         self.w8 = None  # fp8 / int8 / int4 weight copies for decode (LlamaForCausalLM.quantize_weights)
+        # quantized_only: the model's bf16 scratch that "dq" steps dequantize one projection
+        # into, and the [N, K] of each projection whose bf16 weight was released
+        self.dq_scratch: Optional[torch.Tensor] = None
+        self.released: dict = {}
         # the GEMM kernel of each projection and the attention entry, per step size
         self.dispatch = d = LayerDispatch.for_layer(cfg, tp, torch.device(device).type == "cuda")
         self.fast_ok, self.m64_small_ok, self.mw_ok, self.pf_ok, self.attn_fq_ok = (
@@ -273,7 +288,17 @@ class LlamaLayer(nn.Module):
     def _gemm(self, family: str, x: torch.Tensor, name: str, mode: int):
         """Projection `name` of x on the kernel family a Step names (a missing kernel or
         plan raises in the wrapper: no family stands in for another)."""
-        w = getattr(self, name)
+        if family == "w8":
+            q = self.w8[name]
+            return w8_linear(x, q[0], q[1], mode, fmt=q[2])
+        if family == "dq":
+            # One scratch for every projection of every layer: the whole step runs on one
+            # stream, so the GEMM that reads the scratch is enqueued before the next
+            # projection's dequantization overwrites it, and the scratch is dead once that
+            # GEMM is enqueued. Its address never changes, so captured steps replay it.
+            q = self.w8[name]
+            return F.linear(x, dequantize_into(q[0], q[1], q[2], out=self.dq_scratch))
+        w = getattr(self, name)  # (a released bf16 weight raises here: no family stands in for "dq")
         if family == "lib":  # (the eager, host-bound steps first)
             return F.linear(x, w)
         if family == "pf":
@@ -282,9 +307,6 @@ class LlamaLayer(nn.Module):
             return m64_linear(x, w, mode)
         if family == "mw":
             return mw_linear(x, w, mode)
-        if family == "w8":
-            q = self.w8[name]
-            return w8_linear(x, q[0], q[1], mode, fmt=q[2])
         assert family == "skinny", family
         return skinny_linear(x, w, None, mode)
 
@@ -420,8 +442,8 @@ class LlamaLayer(nn.Module):
         h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
         if self.moe:
             return self.mlp(h), residual
-        if step.gate_up == "lib":
-            act = ops.silu_and_mul(F.linear(h, self.gate_up), interleave16=True)
+        if step.gate_up in ("lib", "dq"):  # bf16 gate|up rows out of the library GEMM
+            act = ops.silu_and_mul(self._gemm(step.gate_up, h, "gate_up", MODE_BF16), interleave16=True)
         else:
             act = self._gemm(step.gate_up, h, "gate_up", MODE_SILU)
         if step.down == "lib" and self.tp == 1 and splitk_prefill_ok(act, self.down):
@@ -551,6 +573,8 @@ class LlamaForCausalLM(nn.Module):
         l0 = self.layers[0]
         self.norms_folded = False
         self.weight_dtype = "bf16"
+        self.quantized_only = False     # quantize_weights(kind, quantized_only=True): no bf16 projections
+        self._dq_scratch: Optional[torch.Tensor] = None
         self._fused_ok = l0.fast_ok and l0.attn_fq_ok and H % 1024 == 0 and H // 1024 <= 8
         self._fused_small_ok = self._fused_ok and l0.m64_small_ok
         # every layer on gemm_mw for 64 < T <= MW_MAX_TOKENS (the runner's mixed-step graphs)
@@ -575,14 +599,22 @@ class LlamaForCausalLM(nn.Module):
         return self.quantize_weights("fp8")
 
     @torch.no_grad()
-    def quantize_weights(self, kind: str = "fp8") -> bool:
+    def quantize_weights(self, kind: str = "fp8", quantized_only: bool = False) -> bool:
         """Weight-only quantization for decode batches <= 64 (Req 10.3): per dense
         layer, copies of the QKV / O / gate_up / down weights (after the RMSNorm
         folding) as fp8 (E4M3, per-channel scale), int8 (per-channel scale) or int4
         (per 128-k group scales), run by gemm_w8. Prefill and larger batches keep
         the bf16 weights (MFMA-bound there); the fused bf16 decode layer is
         disabled. Returns False (and changes nothing) when a shape has no gemm_w8
-        plan or the model is MoE."""
+        plan or the model is MoE (Mixtral experts have no quantized form).
+
+        quantized_only: the model is served from the quantized weights alone. Layer
+        by layer, once a layer's copies exist the bf16 storage of its quantized
+        projections is released (peak: the bf16 model plus about one layer), and
+        steps above 64 rows dequantize one projection at a time into one model-wide
+        bf16 scratch of the largest projection that the library GEMM reads
+        (LayerDispatch "dq"). The freed bytes go back to the device, where the
+        engine's KV-pool sizing finds them."""
         fmt = WQ_FORMATS[kind]
         if self.device.type != "cuda" or any(l.moe for l in self.layers):
             return False
@@ -601,10 +633,36 @@ class LlamaForCausalLM(nn.Module):
         chosen = [n for n in names if use_q(n)]
         for l in self.layers:
             l.w8 = {n: quantize_weight(getattr(l, n), fmt) + (fmt,) for n in chosen}
-            l.dispatch.set_quantized(chosen)
+            l.dispatch.set_quantized(chosen, resident=not quantized_only)
+            if quantized_only:
+                for n in chosen:
+                    l.released[n] = tuple(getattr(l, n).shape)
+                    delattr(l, n)  # the parameter and its bf16 storage
         self._fused_ok = self._fused_small_ok = False
         self.weight_dtype = kind
+        if quantized_only:
+            self.quantized_only = True
+            self._mw_ok = False  # (the runner's mixed-step graphs: library-sized, not gemm_mw)
+            self._dq_scratch = torch.empty(max(N * K for l in self.layers for N, K in l.released.values()),
+                                           dtype=torch.bfloat16, device=self.device)
+            for l in self.layers:
+                l.dq_scratch = self._dq_scratch
+            torch.cuda.empty_cache()  # the released weights leave the allocator's cache too
         return True
+
+    def weight_bytes(self) -> int:
+        """Bytes of the weights resident on this rank: every parameter and every quantized
+        copy (codes and scales), without the dequantization scratch."""
+        n = sum(p.numel() * p.element_size() for p in self.parameters())
+        for l in self.layers:
+            for q, s, _ in (l.w8 or {}).values():
+                n += q.numel() * q.element_size() + s.numel() * s.element_size()
+        return n
+
+    def scratch_bytes(self) -> int:
+        """Bytes of the bf16 scratch of a quantized-only model (0 otherwise)."""
+        s = self._dq_scratch
+        return 0 if s is None else s.numel() * s.element_size()
 
     def fused_decode_ok(self, meta: AttnMeta) -> bool:
         T = meta.num_tokens

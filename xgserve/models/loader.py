@@ -29,10 +29,13 @@ def model_class(cfg: ModelConfig):
 
 def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = None,
                 checkpoint: Optional[str] = None, seed: int = 0, tp: Optional[int] = None,
-                rank: Optional[int] = None, weight_dtype: Optional[str] = None):
+                rank: Optional[int] = None, weight_dtype: Optional[str] = None, quantized_only: bool = False):
     """weight_dtype "fp8" / "int8" / "int4": also keep quantized weight copies for
     decode batches <= 64 (LlamaForCausalLM.quantize_weights); activations and
-    everything else stay `dtype`."""
+    everything else stay `dtype`. quantized_only: keep ONLY the quantized projection
+    weights (the bf16 originals are released; larger steps dequantize into a scratch)."""
+    if quantized_only and weight_dtype not in ("fp8", "int8", "int4"):
+        raise ValueError(f"quantized_only needs weight_dtype fp8 / int8 / int4, got {weight_dtype!r}")
     if dtype is None:
         dtype = torch.float32 if (cfg.dtype == "float32" and torch.device(device).type == "cpu") else torch.bfloat16
     m = model_class(cfg)(cfg, device=device, dtype=dtype, tp=tp, rank=rank)
@@ -43,7 +46,7 @@ def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = N
     if hasattr(m, "fold_norms"):
         m.fold_norms()  # RMSNorm weights into the projections (fused decode layer)
     if weight_dtype in ("fp8", "int8", "int4"):
-        if not (hasattr(m, "quantize_weights") and m.quantize_weights(weight_dtype)):
+        if not (hasattr(m, "quantize_weights") and m.quantize_weights(weight_dtype, quantized_only=quantized_only)):
             raise ValueError(f"{weight_dtype} weights are not supported for {cfg.name} on {device}")
     elif weight_dtype not in (None, "bf16", "fp16", "fp32"):
         raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
@@ -178,6 +181,9 @@ def save_checkpoint(model, path: str) -> None:
     """Write a TP=1 model in HF layout (safetensors + config.json)."""
     from safetensors.torch import save_file
     assert model.tp == 1, "save from a TP=1 model"
+    if getattr(model, "quantized_only", False):
+        raise ValueError("save_checkpoint: a quantized-only model has released its bf16 projection weights; "
+                         "save the model before quantize_weights(..., quantized_only=True)")
     cfg = model.cfg
     os.makedirs(path, exist_ok=True)
     t: Dict[str, torch.Tensor] = {}

@@ -695,6 +695,40 @@ def dequantize_weight(q: torch.Tensor, scale: torch.Tensor, fmt: int) -> torch.T
     return {WQ_FP8: dequantize_fp8, WQ_INT8: dequantize_int8, WQ_INT4: dequantize_int4}[fmt](q, scale)
 
 
+def dequantize_into(q: torch.Tensor, scale: torch.Tensor, fmt: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The bf16 weight [N, K] of quantized codes `q` (layouts of quantize_fp8 / _int8 /
+    _int4), bit-identical to dequantize_weight(q, scale, fmt).to(bfloat16): one fp32
+    multiply and one round-to-nearest-even per element (csrc/kernels/dequant.hip).
+    `out`: a contiguous bf16 buffer of at least N * K elements on q's device; the result
+    is the [N, K] view of its first N * K elements (a scratch shared by projections of
+    different shapes). CPU tensors take the PyTorch form."""
+    if fmt not in (WQ_FP8, WQ_INT8, WQ_INT4):
+        raise ValueError(f"dequantize_into: unknown format {fmt!r}")
+    if q.dim() != 2 or q.dtype != torch.uint8 or scale.dtype != torch.float32:
+        raise ValueError(f"dequantize_into: codes must be 2-d uint8 and scales fp32, got {q.dtype} "
+                         f"{tuple(q.shape)} / {scale.dtype}")
+    N = q.shape[0]
+    K = q.shape[1] * 2 if fmt == WQ_INT4 else q.shape[1]
+    if N < 1 or K < 1 or K % WQ_GROUP:
+        raise ValueError(f"dequantize_into: needs N >= 1 and K % {WQ_GROUP} == 0, got N={N} K={K}")
+    if scale.numel() != (N * (K // WQ_GROUP) if fmt == WQ_INT4 else N):
+        raise ValueError(f"dequantize_into: {scale.numel()} scales for N={N} K={K} fmt={fmt}")
+    if scale.device != q.device or not q.is_contiguous() or not scale.is_contiguous():
+        raise ValueError("dequantize_into: codes and scales must be contiguous and on one device")
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=q.device)
+    elif (out.dtype != torch.bfloat16 or out.device != q.device or not out.is_contiguous()
+          or out.numel() < N * K):
+        raise ValueError(f"dequantize_into: out must be a contiguous bf16 buffer of >= {N * K} elements on "
+                         f"{q.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    w = out.view(-1)[:N * K].view(N, K)
+    if not use_native(q):
+        w.copy_(dequantize_weight(q, scale, fmt).to(torch.bfloat16))
+        return w
+    kernels().dequant_w8(q.data_ptr(), scale.data_ptr(), N, K, w.data_ptr(), fmt, stream_ptr())
+    return w
+
+
 def _w8_fits(N: int, K: int, mode: int, S: int, cfg: int, M: int, fmt: int) -> bool:
     cols, kc = W8_CFGS[cfg]
     if N % cols or K % (S * kc) or (M > 16 and cfg >= 3) or (mode == MODE_SILU and (S != 1 or cfg == 2)):
@@ -702,6 +736,7 @@ def _w8_fits(N: int, K: int, mode: int, S: int, cfg: int, M: int, fmt: int) -> b
     return fmt != WQ_INT4 or ((K // S) % WQ_GROUP == 0 and (K // S // WQ_GROUP) * cols <= WQ_SC_FLOATS)
 
 
+@functools.lru_cache(maxsize=None)  # (pure; an eager decode step of a quantized model asks per projection)
 def w8_plan(M: int, N: int, K: int, mode: int, fmt: int = WQ_FP8):
     """(split_k, cfg) for gemm_w8, or None. SiLU needs split 1 and two 16-column
     tiles per wave; otherwise the smallest split-K giving >= 256 workgroups. int4:

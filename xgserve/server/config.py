@@ -100,8 +100,14 @@ class WorkerSection:
     device: Optional[str] = None      # "cpu" forces the CPU path
     # bf16 | fp16 | fp32 | fp8 | int8 | int4: fp8 (E4M3, per-channel scale), int8 (per-channel)
     # and int4 (per 128-k group scales) are weight-only copies for decode batches <= 64,
-    # bf16 activations (Req 10.3; the reference's Q8_0 / Q4_0 levels)
+    # bf16 activations (Req 10.3; the reference's Q8_0 / Q4_0 levels). By default the bf16
+    # weights stay resident beside the copies (larger steps run them), so the footprint
+    # grows; quantized_only releases them -- the model is served from the quantized
+    # weights alone, steps above 64 rows dequantize one projection at a time into a
+    # shared bf16 scratch, and the freed HBM goes to the KV pool (dense Llama models on
+    # a GPU; Mixtral experts are not covered)
     quantization: str = "bf16"
+    quantized_only: bool = False
     block_size: int = 16
     max_num_seqs: int = 256
     max_num_batched_tokens: int = 8192
@@ -201,6 +207,10 @@ class ServerConfig:
             e.append("worker.replicas and worker.tp must be > 0")
         if w.quantization not in ("bf16", "fp16", "fp32", "fp8", "int8", "int4"):
             e.append(f"worker.quantization {w.quantization!r} not supported (bf16|fp16|fp32|fp8|int8|int4)")
+        if w.quantized_only and w.quantization not in ("fp8", "int8", "int4"):
+            e.append(f"worker.quantized_only needs worker.quantization fp8|int8|int4, got {w.quantization!r}")
+        if w.quantized_only and w.device == "cpu":
+            e.append("worker.quantized_only needs a GPU (worker.device is cpu)")
         if not (0.0 < w.gpu_memory_utilization <= 1.0):
             e.append("worker.gpu_memory_utilization must be in (0, 1]")
         if w.block_size % 16:

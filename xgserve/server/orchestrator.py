@@ -983,6 +983,8 @@ class InferenceServer:
             st = dict(r.stats) if r is not None and r.stats else {}
             reps.append({"id": s["id"], "healthy": s["healthy"], "active_requests": len(r.inflight) if r else 0,
                          "memory_used": s["memory_used"], "memory_available": s["memory_available"],
+                         "weight_bytes": st.get("weight_bytes", 0), "scratch_bytes": st.get("scratch_bytes", 0),
+                         "weight_dtype": st.get("weight_dtype"),
                          "kind": r.kind if r else None, "restarts": r.restarts if r else 0,
                          "requests_dispatched": self.dispatched.get(s["id"], 0),
                          "heartbeat_age_s": r.heartbeat_age() if r else None, "engine": st})

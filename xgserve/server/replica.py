@@ -46,6 +46,7 @@ def engine_spec(worker, cache=None, spec=None, fault: Optional[dict] = None, bat
     wdt = worker.quantization if worker.quantization in ("fp8", "int8", "int4") else None
     return dict(mock=worker.mock, mock_latency_ms=worker.mock_latency_ms, mock_kv_seqs=worker.mock_kv_seqs, model=worker.model,
                 checkpoint=worker.checkpoint, tp=worker.tp, device=worker.device, dtype=dt, weight_dtype=wdt,
+                quantized_only=worker.quantized_only,
                 block_size=worker.block_size, max_num_seqs=worker.max_num_seqs,
                 max_num_batched_tokens=worker.max_num_batched_tokens, max_model_len=worker.max_model_len,
                 gpu_memory_utilization=worker.gpu_memory_utilization, num_blocks=worker.num_blocks,
