@@ -126,6 +126,15 @@ __global__ void __launch_bounds__(1024) argmax_kernel(const T* __restrict__ logi
 // Gumbel-max sampling with optional top-k / top-p thresholds.
 // temps[row] <= 0 means greedy for that row.
 // --------------------------------------------------------------------------
+// y = logit / T, rounded to fp32 on its own. Every pass of both samplers must see the
+// same y: a product contracted into `M - y` (one fma) in one kernel and rounded in
+// another puts a token next to a bin edge into different bins in the two, and the draw
+// then drops a token the histograms counted as kept.
+__device__ __forceinline__ float scaled_logit(float x, float it) {
+#pragma clang fp contract(off)
+  return x * it;
+}
+
 template <typename T>
 __device__ float block_reduce_max(float v, float* sh) {
   v = wave_max(v);
@@ -167,8 +176,9 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
   // pass 1: row max and log-sum-exp of logits/T
   float mx = -INFINITY, se = 0.f;
   for (int i = threadIdx.x; i < V; i += blockDim.x) {
-    const float x = scalar_at<T>(row, i) * it;
-    if (x > mx) { se = se * __expf(mx - x) + 1.f; mx = x; } else { se += __expf(x - mx); }
+    const float x = scaled_logit(scalar_at<T>(row, i), it);
+    // x == mx == -inf (a masked logit before the first finite one) adds nothing, not NaN
+    if (x > mx) { se = se * __expf(mx - x) + 1.f; mx = x; } else if (x != -INFINITY) { se += __expf(x - mx); }
   }
   const float M = block_reduce_max<T>(mx, sh);
   const float S = block_reduce_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
@@ -185,7 +195,7 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
       const float mid_p = 0.5f * (lo_p + hi_p), mid_k = 0.5f * (lo_k + hi_k);
       float mass = 0.f, cnt = 0.f;
       for (int i = threadIdx.x; i < V; i += blockDim.x) {
-        const float x = scalar_at<T>(row, i) * it;
+        const float x = scaled_logit(scalar_at<T>(row, i), it);
         if (x >= mid_p) mass += __expf(x - logZ);
         if (x >= mid_k) cnt += 1.f;
       }
@@ -206,12 +216,13 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
                               hash32(static_cast<uint32_t>(step) * 0x27d4eb2fU + 0x165667b1U));
   ArgLse a{-INFINITY, 0x7fffffff, -INFINITY, 0.f};
   for (int i = threadIdx.x; i < V; i += blockDim.x) {
-    const float x = scalar_at<T>(row, i) * it;
+    const float x = scaled_logit(scalar_at<T>(row, i), it);
     if (x < thr) continue;
     float score = x;
     if (!greedy) {
       const uint32_t hsh = hash32(key ^ hash32(static_cast<uint32_t>(i) * 0x9E3779B9U));
-      const float u = (static_cast<float>(hsh >> 8) + 0.5f) * (1.f / 16777216.f);
+      // 23 bits: n + 0.5 is exact in fp32, so u stays inside [2^-24, 1 - 2^-24]
+      const float u = (static_cast<float>(hsh >> 9) + 0.5f) * (1.f / 8388608.f);
       score = x - __logf(-__logf(u));
     }
     if (score > a.v) { a.v = score; a.i = i; a.m = x; }
@@ -376,7 +387,7 @@ __global__ void __launch_bounds__(samp::NT) samp_stats_kernel(const T* __restric
   samp_chunk(V, P, p, sr.lo, sr.hi);
   float m = -INFINITY, sv = 0.f;
   sr.visit([&](int, float x) {
-    const float y = x * it;
+    const float y = scaled_logit(x, it);
     if (y > m) { sv = (m == -INFINITY ? 0.f : sv * __expf(m - y)) + 1.f; m = y; } else { sv += __expf(y - m); }
   });
   __shared__ float rm[samp::NT / 64], rs[samp::NT / 64];
@@ -517,7 +528,7 @@ __global__ void __launch_bounds__(samp::NT) samp_hist_kernel(const T* __restrict
   SampRow<T> sr{logits + b * stride, 0, 0};
   samp_chunk(V, P, p, sr.lo, sr.hi);
   sr.visit([&](int, float x) {
-    const float y = x * q.it;
+    const float y = scaled_logit(x, q.it);
     int sub;
     const int bin = samp_bin(M - y, sub);
     if (bin >= samp::NB) return;
@@ -580,12 +591,13 @@ __global__ void __launch_bounds__(samp::NT) samp_draw_kernel(const T* __restrict
   SampRow<T> sr{logits + b * stride, 0, 0};
   samp_chunk(V, P, p, sr.lo, sr.hi);
   const bool filt = q.use_p || q.use_k;
-  // Gumbel noise is bounded: u <= 1 - 2^-25 gives -log(-log u) < 17.33, so a token with
-  // y + GMAX below this thread's best score cannot win -- skipped without its hash
-  // (exact: the draw is unchanged)
+  // Gumbel noise is bounded: u = (n + 0.5) / 2^23 with n < 2^23 is exact in fp32 (24
+  // significant bits; a 24-bit n would round n + 0.5 up to 2^24, u = 1, noise +inf), so
+  // u <= 1 - 2^-24 and -log(-log u) < 16.64: a token with y + GMAX below this thread's
+  // best score cannot win -- skipped without its hash (exact: the draw is unchanged)
   constexpr float GMAX = 17.5f;
   sr.visit([&](int i, float x) {
-    const float y = x * q.it;
+    const float y = scaled_logit(x, q.it);
     if (!q.greedy && y + GMAX < bv) return;
     if (filt && y < M) {  // the row max is always kept
       int sub;
@@ -597,7 +609,7 @@ __global__ void __launch_bounds__(samp::NT) samp_draw_kernel(const T* __restrict
     float score = y;
     if (!q.greedy) {
       const uint32_t hsh = hash32(key ^ hash32(static_cast<uint32_t>(i) * 0x9E3779B9U));
-      const float uu = (static_cast<float>(hsh >> 8) + 0.5f) * (1.f / 16777216.f);
+      const float uu = (static_cast<float>(hsh >> 9) + 0.5f) * (1.f / 8388608.f);
       score = y - __logf(-__logf(uu));
     }
     if (score > bv) { bv = score; bi = i; by = y; }
