@@ -1,20 +1,8 @@
-// gemm_m64 with LDS-DMA (global_load_lds_dwordx4) staging for BOTH operands.
-//
-// Same contract as gemm_m64 (16 < M <= 64, out = x . W^T, split-K partials /
-// bf16 / fused SiLU-gate), different load path: the register-ring kernel feeds
-// W to the MFMAs as fragment-shaped loads (16 rows x 64 B per wave instruction),
-// which keeps the texture-address path busy at ~4 TB/s chip-wide; here every
-// wave instruction moves 4 rows x 256 B (full lines) straight into LDS:
-//   * K chunk = 128 (256 B per row); 3 LDS slots, 2 chunks in flight;
-//   * W: each wave DMAs its own 16*NW rows into a wave-private region of the
-//     slot; x: the 4 waves DMA 64 rows x 256 B (4 instructions each);
-//   * LDS images are lane-linear (DMA writes base + lane*16) with the 16-B
-//     granule XOR-swizzle (granule ^ (row & 15)) applied on the GLOBAL source
-//     address, and undone on the ds_read_b128 fragment reads (conflict-free);
-//   * one raw s_barrier per chunk after a COUNTED vmcnt (the next chunk stays in
-//     flight across it), never __syncthreads (its fence would drain the DMA
-//     queue); WAR: a slot is re-filled only after the barrier that follows its
-//     last reads (cdna_hip_programming.md §5 "Pipelining across barriers").
+// gemm_m64g: out = x . W^T for M <= 64 rows (decode batches) on the LDS-DMA pipeline of
+// m64_pipe.h (both operands staged by global_load_lds_dwordx4, three-slot ring, counted
+// vmcnt + one raw barrier per K chunk); split-K partials / bf16 / fused SiLU-gate. Dense
+// form (gemm_m64g_kernel, also with deeper rings at M <= 16) and grouped MoE form
+// (gemm_m64g_grouped_kernel).
 //
 // Fused decode layer (M64Epi; dense Llama decode path, xgserve/models/llama.py):
 //   * the input RMSNorm as an epilogue row scale: x is the raw bf16 residual
@@ -35,7 +23,8 @@
 
 #include <algorithm>
 
-#include "glds.h"
+#include "m64_pipe.h"
+#include "m64g_api.h"
 #include "../comm/ll.h"
 
 namespace xgk {
@@ -97,23 +86,6 @@ struct ArDesc {
   uint32_t* err;                 // [timeouts, wait limit] (the custom all-reduce's ctl)
   float* ss_tmp;
   int* pair;
-};
-
-// GG_MOE_RESID (grouped w2 of the fused decode layer, TP = 1): the MoE combine inside
-// the w2 launch. Every workgroup stores its fp32 partial rows write-through and takes a
-// ticket on its column tile; the tile's last arriver (all real row tiles x S splits
-// have stored) adds, per token t, sum_j w[t, j] * sum_s part[s, dest[t, j]] over the
-// tile's columns into the bf16 residual stream and writes the new residual's sum of
-// squares ss_out[tile * T + t] (the next RMSNorm reads N / cols partial sums per row).
-// Replaces the separate combine_resid launch (6 us per layer at Mixtral batch 1).
-struct MoeResidEpi {
-  const int32_t* dest;   // [T * k] padded row of each (token, choice), -1 = not local
-  const float* w;        // [T * k] routing weights
-  uint16_t* resid;       // [T, N] bf16 residual stream, updated in place
-  float* ss_out;         // [N / cols, T]
-  int* counters;         // one ticket per column tile, zero between launches
-  int T;
-  int k;
 };
 
 // K-chunk rotation. Workgroups that all start at K chunk 0 and walk in lockstep read the
@@ -444,18 +416,8 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_kernel(const uint16_t* _
                                                                const uint16_t* __restrict__ w, int N,
                                                                float* __restrict__ part, uint16_t* __restrict__ out,
                                                                int mode, M64Epi epi) {
-  constexpr int RB = KC * 2;                     // bytes per LDS row
-  constexpr int GPR = KC / 8;                    // 16-B granules per row
-  constexpr int RPI = 1024 / RB;                 // rows per DMA instruction (64 lanes x 16 B)
-  constexpr int XROWS = 16 * MT;
-  constexpr int XBYTES = XROWS * RB;
-  constexpr int XI = XROWS / RPI / WV;           // x DMA instructions per wave per chunk
-  constexpr int WROWS = 16 * NW;                 // weight rows per wave
-  constexpr int WI = WROWS / RPI;                // weight DMA instructions per wave per chunk
-  constexpr int WBYTES = WROWS * RB;             // per wave per slot
-  constexpr int SLOT = XBYTES + WV * WBYTES;
-  constexpr int G = XI + WI;
-  static_assert(XI >= 1 && WI >= 1 && XROWS % (RPI * WV) == 0, "bad m64g geometry");
+  using GM = M64Geom<NW, WV, KC, MT>;
+  constexpr int SLOT = GM::SLOT, G = GM::G;
   static_assert(NS >= 3 && NS * SLOT <= 160 * 1024, "ring");
   __shared__ __attribute__((aligned(1024))) uint8_t lds0[NS == 3 ? SLOT : NS * SLOT];
   __shared__ __attribute__((aligned(1024))) uint8_t lds1[NS == 3 ? SLOT : 16];
@@ -471,77 +433,29 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_kernel(const uint16_t* _
   const int c_lo = s * nch_all / S;
   const int k0 = c_lo * KC;
   const int nchunks = (s + 1) * nch_all / S - c_lo;
-  const int nbase = bx * (16 * NW * WV) + wid * WROWS;
+  const int nbase = bx * GM::COLS + wid * GM::WROWS;
 
-  const int dr = lane / GPR, dj = lane % GPR;    // row within a DMA instruction, granule
-  const uint16_t* wsrc[WI];
+  const uint16_t* wsrc[GM::WI];
 #pragma unroll
-  for (int i = 0; i < WI; ++i) {
-    const int r = RPI * i + dr;
-    wsrc[i] = w + static_cast<int64_t>(nbase + r) * K + k0 + 8 * (dj ^ (r & (GPR - 1)));
+  for (int i = 0; i < GM::WI; ++i) {
+    const int r = GM::w_row(i, lane);
+    wsrc[i] = w + static_cast<int64_t>(nbase + r) * K + k0 + 8 * GM::w_gran(r, lane);
   }
-  const uint16_t* xsrc[XI];
+  const uint16_t* xsrc[GM::XI];
 #pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const int r = RPI * (wid * XI + i) + dr;     // x row 0..XROWS-1
-    xsrc[i] = x + static_cast<int64_t>(min(r, M - 1)) * K + k0 + 8 * (dj ^ (r & (GPR - 1)));
+  for (int i = 0; i < GM::XI; ++i) {
+    const int r = GM::x_row(wid, i, lane);       // x row 0..XROWS-1
+    xsrc[i] = x + static_cast<int64_t>(min(r, M - 1)) * K + k0 + 8 * GM::x_gran(r, lane);
   }
   const int rot = epi.krot ? static_cast<int>((static_cast<unsigned>(bx) * 37u) % static_cast<unsigned>(nchunks)) : 0;
-
-  auto chunk_k = [&](int c) {
-    const int cr = c + rot;
-    return (cr >= nchunks ? cr - nchunks : cr) * KC;
-  };
-  auto issue_x = [&](uint8_t* slot, int c) {
-    const int kk = chunk_k(c);
-#pragma unroll
-    for (int i = 0; i < XI; ++i) glds16(xsrc[i] + kk, slot + RPI * (wid * XI + i) * RB);
-  };
-  auto issue_w = [&](uint8_t* slot, int c) {
-    const int kk = chunk_k(c);
-#pragma unroll
-    for (int i = 0; i < WI; ++i) {
-      if constexpr (NT) glds16_nt(wsrc[i] + kk, slot + XBYTES + wid * WBYTES + i * 1024);
-      else glds16(wsrc[i] + kk, slot + XBYTES + wid * WBYTES + i * 1024);
-    }
-  };
   auto issue = [&](uint8_t* slot, int c) {
-    issue_x(slot, c);
-    issue_w(slot, c);
+    const int cr = c + rot;
+    const int kk = (cr >= nchunks ? cr - nchunks : cr) * KC;
+    m64_issue<GM, NT>(slot, wid, xsrc, kk, wsrc, kk);
   };
-
   f32x4_t acc[NW][MT];
-#pragma unroll
-  for (int nt = 0; nt < NW; ++nt)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](const uint8_t* slot) {
-    const uint8_t* xs = slot;
-    const uint8_t* ws = slot + XBYTES + wid * WBYTES;
-#pragma unroll
-    for (int t = 0; t < KC / 32; ++t) {
-      const int phys = (4 * t + g) ^ (li & (GPR - 1));
-      uint4 b[MT], a[NW];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) b[mt] = *reinterpret_cast<const uint4*>(xs + (16 * mt + li) * RB + phys * 16);
-#pragma unroll
-      for (int nt = 0; nt < NW; ++nt) a[nt] = *reinterpret_cast<const uint4*>(ws + (16 * nt + li) * RB + phys * 16);
-#pragma unroll
-      for (int nt = 0; nt < NW; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = mfma16x16x32(as_frag(a[nt]), as_frag(b[mt]), acc[nt][mt]);
-    }
-  };
-
-  // chunk c lives in slot c % 3; per chunk: counted wait (chunk c+1 stays in
-  // flight), barrier, DMA chunk c+2 into the slot freed by that barrier, compute c
-  auto step = [&](uint8_t* cur, uint8_t* nxt2, int c) {
-    if (c + 1 < nchunks) wait_vmcnt<G>();
-    else wait_vmcnt<0>();
-    raw_barrier();
-    if (c + 2 < nchunks) issue(nxt2, c + 2);
-    compute(cur);
-  };
+  m64_zero(acc);
+  auto compute = [&](const uint8_t* slot, int) { m64_compute_bf16<GM>(slot, wid, g, li, acc); };
 
   // RMSNorm statistics of the input rows, loaded before the weight stream starts
   // (clamped unconditional loads, masked when combined; held in 8 registers)
@@ -577,14 +491,7 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_kernel(const uint16_t* _
     if (j < nchunks) issue(slot_of(j), j);
 
   if constexpr (NS == 3) {
-    int c = 0;
-    for (; c + 3 <= nchunks; c += 3) {
-      step(lds0, lds2, c);
-      step(lds1, lds0, c + 1);
-      step(lds2, lds1, c + 2);
-    }
-    if (c < nchunks) step(lds0, lds2, c);
-    if (c + 1 < nchunks) step(lds1, lds0, c + 1);
+    m64_ring<G>(lds0, lds1, lds2, nchunks, issue, compute);
   } else {
     // NS-slot ring: chunk c in slot c % NS; before chunk c the chunks after it that
     // are already issued (rem = min(nchunks - 1 - c, NS - 2)) stay in flight
@@ -603,7 +510,7 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_kernel(const uint16_t* _
       if (rem == 0) wait_vmcnt<0>();
       raw_barrier();
       if (c + NS - 1 < nchunks) issue(lds0 + ((c + NS - 1) % NS) * SLOT, c + NS - 1);
-      compute(lds0 + (c % NS) * SLOT);
+      compute(lds0 + (c % NS) * SLOT, c);
     }
   }
 
@@ -667,7 +574,7 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_kernel(const uint16_t* _
   if (mode == GG_AR) ar_dv = reinterpret_cast<const uint32_t*>(epi.ar)[lane < 30 ? lane : 29];
   // acc[nt][mt][r] = out[m = 16 mt + li][n = nbase + 16 nt + 4 g + r]
   const bool silu_split = NW == 2 && mode == GG_SILU && S > 1;
-  constexpr int TCOLS = 16 * NW * WV;
+  constexpr int TCOLS = GM::COLS;
   if ((mode == GG_AR || mode == GG_RESID) && S == 1 && 256 + M * TCOLS * 4 <= static_cast<int>(sizeof(lds0))) {
     // one split: the tile goes through LDS to the residual / all-reduce tail (no slab
     // store + drain + reload)
@@ -685,54 +592,17 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_kernel(const uint16_t* _
     if (mode == GG_AR) m64g_ar_tail<TCOLS, 64 * WV>(part, S, M, N, epi, reinterpret_cast<int*>(lds0), bx, ar_dv, ys);
     else m64g_resid_tail<TCOLS, 64 * WV>(part, S, M, N, epi, reinterpret_cast<int*>(lds0), bx, ys);
   } else if (mode == GG_PARTIAL || mode == GG_RESID || mode == GG_AR || silu_split) {
-    float* pp = part + static_cast<int64_t>(s) * M * N;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int m = 16 * mt + li;
-      if (m >= M) continue;
-#pragma unroll
-      for (int nt = 0; nt < NW; ++nt) {
-        float* dst = pp + static_cast<int64_t>(m) * N + nbase + 16 * nt + 4 * g;
-        if (mode != GG_PARTIAL) st16_sc1(dst, acc[nt][mt]);
-        else *reinterpret_cast<float4*>(dst) = make_float4(acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]);
-      }
-    }
+    m64_store_f32<true>(acc, part + static_cast<int64_t>(s) * M * N, 0, M, N, nbase, g, li, mode != GG_PARTIAL);
     if (mode == GG_RESID)
-      m64g_resid_tail<16 * NW * WV, 64 * WV>(part, S, M, N, epi, reinterpret_cast<int*>(lds0), bx);
+      m64g_resid_tail<TCOLS, 64 * WV>(part, S, M, N, epi, reinterpret_cast<int*>(lds0), bx);
     else if (mode == GG_AR)
-      m64g_ar_tail<16 * NW * WV, 64 * WV>(part, S, M, N, epi, reinterpret_cast<int*>(lds0), bx, ar_dv);
+      m64g_ar_tail<TCOLS, 64 * WV>(part, S, M, N, epi, reinterpret_cast<int*>(lds0), bx, ar_dv);
     else if (silu_split)
-      m64g_silu_tail<16 * NW * WV, 64 * WV>(part, S, M, N, out, epi.counters, reinterpret_cast<int*>(lds0), bx);
+      m64g_silu_tail<TCOLS, 64 * WV>(part, S, M, N, out, epi.counters, reinterpret_cast<int*>(lds0), bx);
   } else if (mode == GG_BF16) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int m = 16 * mt + li;
-      if (m >= M) continue;
-#pragma unroll
-      for (int nt = 0; nt < NW; ++nt) {
-        uint2 v;
-        v.x = pack2(acc[nt][mt][0], acc[nt][mt][1]);
-        v.y = pack2(acc[nt][mt][2], acc[nt][mt][3]);
-        *reinterpret_cast<uint2*>(out + static_cast<int64_t>(m) * N + nbase + 16 * nt + 4 * g) = v;
-      }
-    }
-  } else if (NW == 2) {
-    const int F = N / 2, f0 = nbase / 2 + 4 * g;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int m = 16 * mt + li;
-      if (m >= M) continue;
-      float o[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float gt = acc[0][mt][r];
-        o[r] = gt / (1.f + __expf(-gt)) * acc[NW - 1][mt][r];
-      }
-      uint2 v;
-      v.x = pack2(o[0], o[1]);
-      v.y = pack2(o[2], o[3]);
-      *reinterpret_cast<uint2*>(out + static_cast<int64_t>(m) * F + f0) = v;
-    }
+    m64_store_bf16<true>(acc, out, 0, M, N, nbase, g, li);
+  } else if constexpr (NW == 2) {
+    m64_store_silu<true>(acc, out, 0, M, N / 2, nbase, g, li);
   }
 }
 
@@ -788,152 +658,60 @@ __device__ __forceinline__ void moe_resid_tail(const float* __restrict__ part, i
 
 template <int NW, int WV, int KC, bool NT, int MT>
 __device__ __forceinline__ void grouped_body(const uint16_t* __restrict__ x, const int32_t* __restrict__ rows, int e,
-                                             int p0, int p1, int rt0, int K, const uint16_t* __restrict__ w, int N,
+                                             int p0, int p1, int rt, int K, const uint16_t* __restrict__ w, int N,
                                              int P, float* __restrict__ part, uint16_t* __restrict__ out, int mode,
                                              uint8_t* lds0, uint8_t* lds1, uint8_t* lds2, int krot,
                                              const MoeResidEpi& mre, int contributors) {
-  constexpr int RB = KC * 2;
-  constexpr int GPR = KC / 8;
-  constexpr int RPI = 1024 / RB;
-  constexpr int XROWS = 16 * MT;
-  constexpr int XBYTES = XROWS * RB;
-  constexpr int XI = XROWS / RPI / WV;
-  constexpr int WROWS = 16 * NW;
-  constexpr int WI = WROWS / RPI;
-  constexpr int WBYTES = WROWS * RB;
-  constexpr int G = XI + WI;
-  static_assert(XI >= 1 && WI >= 1 && XROWS % (RPI * WV) == 0, "bad m64g geometry");
+  using GM = M64Geom<NW, WV, KC, MT>;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
   const int S = gridDim.y, s = blockIdx.y;
   const int kws = K / S;
   const int k0 = s * kws;
   const int nchunks = kws / KC;
-  const int nbase = blockIdx.x * (16 * NW * WV) + wid * WROWS;
-  const int dr = lane / GPR, dj = lane % GPR;
+  const int nbase = blockIdx.x * GM::COLS + wid * GM::WROWS;
   const uint16_t* we = w + static_cast<int64_t>(e) * N * K;
-  const uint16_t* wsrc[WI];
+  const uint16_t* wsrc[GM::WI];
 #pragma unroll
-  for (int i = 0; i < WI; ++i) {
-    const int r = RPI * i + dr;
-    wsrc[i] = we + static_cast<int64_t>(nbase + r) * K + k0 + 8 * (dj ^ (r & (GPR - 1)));
+  for (int i = 0; i < GM::WI; ++i) {
+    const int r = GM::w_row(i, lane);
+    wsrc[i] = we + static_cast<int64_t>(nbase + r) * K + k0 + 8 * GM::w_gran(r, lane);
   }
   // non-temporal weight loads only when each expert's column tile is read once
   // (one 64-row tile); with several row tiles the re-reads should hit L2/MALL
-  const bool nt = NT && (p1 - p0) <= 64;
+  const bool nt = (p1 - p0) <= 64;
+  // x rows gathered through the layout; a pad row reads the tile's first row
+  const int first = rows ? rows[rt] : rt;
+  const uint16_t* xsrc[GM::XI];
+#pragma unroll
+  for (int i = 0; i < GM::XI; ++i) {
+    const int r = GM::x_row(wid, i, lane);
+    int src = rows ? rows[rt + r] : rt + r;
+    if (src < 0) src = first;
+    xsrc[i] = x + static_cast<int64_t>(src) * K + k0 + 8 * GM::x_gran(r, lane);
+  }
+  // K-chunk rotation (k_rotation): expert e's column tiles spread over K
+  const int rot = krot ? static_cast<int>((blockIdx.x * 37u + e * 11u) % static_cast<unsigned>(nchunks)) : 0;
+  auto issue = [&](uint8_t* slot, int c) {
+    const int cr = c + rot;
+    const int kk = (cr >= nchunks ? cr - nchunks : cr) * KC;
+    m64_issue<GM, NT>(slot, wid, xsrc, kk, wsrc, kk, nt);
+  };
+  f32x4_t acc[NW][MT];
+  m64_zero(acc);
+  m64_ring_prologue(lds0, lds1, nchunks, issue);
+  m64_ring<GM::G>(lds0, lds1, lds2, nchunks, issue,
+                  [&](const uint8_t* slot, int) { m64_compute_bf16<GM>(slot, wid, g, li, acc); });
 
-  {
-    const int rt = rt0;
-    const int first = rows ? rows[rt] : rt;
-    const uint16_t* xsrc[XI];
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      const int r = RPI * (wid * XI + i) + dr;
-      int src = rows ? rows[rt + r] : rt + r;
-      if (src < 0) src = first;
-      xsrc[i] = x + static_cast<int64_t>(src) * K + k0 + 8 * (dj ^ (r & (GPR - 1)));
-    }
-    // K-chunk rotation (k_rotation): expert e's column tiles spread over K
-    const int rot = krot ? static_cast<int>((blockIdx.x * 37u + e * 11u) % static_cast<unsigned>(nchunks)) : 0;
-    auto issue = [&](uint8_t* slot, int c) {
-      const int cr = c + rot;
-      const int kk = (cr >= nchunks ? cr - nchunks : cr) * KC;
-#pragma unroll
-      for (int i = 0; i < XI; ++i) glds16(xsrc[i] + kk, slot + RPI * (wid * XI + i) * RB);
-      if (nt) {
-#pragma unroll
-        for (int i = 0; i < WI; ++i) glds16_nt(wsrc[i] + kk, slot + XBYTES + wid * WBYTES + i * 1024);
-      } else {
-#pragma unroll
-        for (int i = 0; i < WI; ++i) glds16(wsrc[i] + kk, slot + XBYTES + wid * WBYTES + i * 1024);
-      }
-    };
-    f32x4_t acc[NW][MT];
-#pragma unroll
-    for (int nt_ = 0; nt_ < NW; ++nt_)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[nt_][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](const uint8_t* slot) {
-      const uint8_t* xs = slot;
-      const uint8_t* ws = slot + XBYTES + wid * WBYTES;
-#pragma unroll
-      for (int t = 0; t < KC / 32; ++t) {
-        const int phys = (4 * t + g) ^ (li & (GPR - 1));
-        uint4 b[MT], a[NW];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-          b[mt] = *reinterpret_cast<const uint4*>(xs + (16 * mt + li) * RB + phys * 16);
-#pragma unroll
-        for (int nt_ = 0; nt_ < NW; ++nt_)
-          a[nt_] = *reinterpret_cast<const uint4*>(ws + (16 * nt_ + li) * RB + phys * 16);
-#pragma unroll
-        for (int nt_ = 0; nt_ < NW; ++nt_)
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) acc[nt_][mt] = mfma16x16x32(as_frag(a[nt_]), as_frag(b[mt]), acc[nt_][mt]);
-      }
-    };
-    auto step = [&](uint8_t* cur, uint8_t* nxt2, int c) {
-      if (c + 1 < nchunks) wait_vmcnt<G>();
-      else wait_vmcnt<0>();
-      raw_barrier();
-      if (c + 2 < nchunks) issue(nxt2, c + 2);
-      compute(cur);
-    };
-    issue(lds0, 0);
-    if (nchunks > 1) issue(lds1, 1);
-    int c = 0;
-    for (; c + 3 <= nchunks; c += 3) {
-      step(lds0, lds2, c);
-      step(lds1, lds0, c + 1);
-      step(lds2, lds1, c + 2);
-    }
-    if (c < nchunks) step(lds0, lds2, c);
-    if (c + 1 < nchunks) step(lds1, lds0, c + 1);
-
-    if (mode == GG_PARTIAL || mode == GG_MOE_RESID) {
-      float* pp = part + static_cast<int64_t>(s) * P * N;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int m = rt + 16 * mt + li;
-#pragma unroll
-        for (int nt_ = 0; nt_ < NW; ++nt_) {
-          float* dst = pp + static_cast<int64_t>(m) * N + nbase + 16 * nt_ + 4 * g;
-          if (mode == GG_MOE_RESID) st16_sc1(dst, acc[nt_][mt]);
-          else *reinterpret_cast<float4*>(dst) = make_float4(acc[nt_][mt][0], acc[nt_][mt][1], acc[nt_][mt][2],
-                                                             acc[nt_][mt][3]);
-        }
-      }
-      if (mode == GG_MOE_RESID) moe_resid_tail<16 * NW * WV, 64 * WV>(part, S, P, N, mre, contributors,
-                                                                       reinterpret_cast<int*>(lds0), blockIdx.x);
-    } else if (mode == GG_BF16) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int m = rt + 16 * mt + li;
-#pragma unroll
-        for (int nt_ = 0; nt_ < NW; ++nt_) {
-          uint2 v;
-          v.x = pack2(acc[nt_][mt][0], acc[nt_][mt][1]);
-          v.y = pack2(acc[nt_][mt][2], acc[nt_][mt][3]);
-          *reinterpret_cast<uint2*>(out + static_cast<int64_t>(m) * N + nbase + 16 * nt_ + 4 * g) = v;
-        }
-      }
-    } else if (NW == 2) {
-      const int F = N / 2, f0 = nbase / 2 + 4 * g;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int m = rt + 16 * mt + li;
-        float o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float gt = acc[0][mt][r];
-          o[r] = gt / (1.f + __expf(-gt)) * acc[NW - 1][mt][r];
-        }
-        uint2 v;
-        v.x = pack2(o[0], o[1]);
-        v.y = pack2(o[2], o[3]);
-        *reinterpret_cast<uint2*>(out + static_cast<int64_t>(m) * F + f0) = v;
-      }
-    }
+  // rows are not guarded: a body writes all of its 16 * MT rows (pads past the real ones)
+  if (mode == GG_PARTIAL || mode == GG_MOE_RESID) {
+    m64_store_f32<false>(acc, part + static_cast<int64_t>(s) * P * N, rt, 0, N, nbase, g, li, mode == GG_MOE_RESID);
+    if (mode == GG_MOE_RESID) moe_resid_tail<GM::COLS, 64 * WV>(part, S, P, N, mre, contributors,
+                                                                reinterpret_cast<int*>(lds0), blockIdx.x);
+  } else if (mode == GG_BF16) {
+    m64_store_bf16<false>(acc, out, rt, 0, N, nbase, g, li);
+  } else if constexpr (NW == 2) {
+    m64_store_silu<false>(acc, out, rt, 0, N / 2, nbase, g, li);
   }
 }
 
@@ -1027,8 +805,6 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_grouped_kernel(const uin
   if constexpr (MT1_OK)
     grouped_body<NW, WV, KC, NT, 1>(x, rows, e, p0, p1, rt0, K, w, N, P, part, out, mode, lds0, lds1, lds2, krot, mre, contributors);
 }
-
-int m64g_cfg_kc(int cfg);
 
 template <int NW>
 static void launch_m64g_grouped(int cfg, dim3 grid, hipStream_t st, const uint16_t* x, const int32_t* rows,

@@ -2,8 +2,9 @@
 // bf16 activations: out = x . (diag(s) W8)^T for M <= 64 (decode batches).
 //
 // Weight-only FP8 halves the bytes of a bandwidth-bound decode step. The weights
-// stream through the same LDS-DMA pipeline as gemm_m64g (3 slots, 2 chunks in
-// flight, counted vmcnt + raw barrier, non-temporal weight DMA); each A fragment is
+// stream through the same LDS-DMA pipeline as gemm_m64g (described in m64_pipe.h: 3
+// slots, 2 chunks in flight, counted vmcnt + raw barrier, non-temporal weight DMA),
+// written out here (see the note above the kernel); each A fragment is
 // read as 8 fp8 bytes and widened to bf16 in registers with v_cvt_scalef32_pk_bf16_fp8
 // (exact: every E4M3 value is representable in bf16), then the bf16 MFMA
 // (16x16x32) runs as in the bf16 kernel. The per-channel scale is applied to the
@@ -33,6 +34,7 @@
 //            workgroup's scales are staged in LDS before the DMA pipeline starts
 //            (no VGPR-destination global load beside the in-flight LDS-DMA).
 #include "glds.h"
+#include "m64g_api.h"
 
 namespace xgk {
 
@@ -81,6 +83,11 @@ __device__ __forceinline__ bf16x8_t fp8x8_to_bf16(uint2 v) {
 //   NW  16-column MFMA tiles per wave (SiLU needs 2: one gate + one up tile)
 //   WV  waves per workgroup
 //   KC  k per chunk (fp8 row = KC bytes, bf16 x row = 2 KC bytes)
+// The ring and the stores are this kernel's own copy of m64_pipe.h's (M64Geom takes the
+// weight row bytes for it): hipcc contracts the int4 `fold` into FMAs differently when
+// they are inlined from the helpers (it changes int4 outputs in the last bit and the
+// batch-1 int4 step by +0.6 %, profiles/m64_pipe_refactor.md). Pin the fold's
+// arithmetic with explicit fmaf before moving this kernel onto the header.
 template <int NW, int WV, int KC, int MT, int FMT = WQ_FP8>
 __global__ void __launch_bounds__(64 * WV, 1) gemm_w8_kernel(const uint16_t* __restrict__ x, int M, int K,
                                                              const uint8_t* __restrict__ w,

@@ -11,6 +11,8 @@
 #include <cstring>
 #include <pybind11/stl.h>
 
+#include "m64g_api.h"
+
 namespace py = pybind11;
 
 namespace xgk {
@@ -20,18 +22,11 @@ void layernorm(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, int
 void silu_and_mul(const uint16_t*, uint16_t*, int, int, int, hipStream_t);
 int skinny_gemm(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, hipStream_t);
 int skinny_slab_kmax(int);
-int gemm_m64g(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, int, int, hipStream_t);
-int gemm_m64g_ex(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, int, int, const float*,
-                 int, int, float, uint16_t*, float*, int*, hipStream_t);
 int gemm_mw(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, int, hipStream_t);
-int gemm_m64g_ar(const uint16_t*, int, int, const uint16_t*, int, float*, int, int, int, uint16_t*, float*, int*,
-                 const void*, hipStream_t);
-int m64g_ar_desc_bytes();
 int gemm_pf_grouped(const uint16_t*, const int32_t*, const int32_t*, int, int, int, const uint16_t*, int, int, float*,
                     uint16_t*, int, int, int, hipStream_t);
 int gemm_pf(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, int, hipStream_t);
 void set_pf_krot(int);
-void set_k_rotation(int mode);
 void add_partials_resid(const float*, int, int, uint16_t*, float*, int, hipStream_t, uint64_t);
 void row_sumsq(const uint16_t*, int, int, float*, hipStream_t);
 void embed_gather(const int32_t*, int, const uint16_t*, int, int, uint16_t*, float*, hipStream_t);
@@ -39,18 +34,6 @@ void mean_l2norm_rows(float*, const int32_t*, const int32_t*, float*, int, int, 
 int decode_attention_fq(const float*, int, const int32_t*, const float*, const int32_t*, uint16_t*, uint16_t*,
                         const int32_t*, int, const int32_t*, float*, float*, uint16_t*, int64_t, int, int, int, int,
                         int, float, int, int, hipStream_t, int);
-struct MoeResidEpi {
-  const int32_t* dest;
-  const float* w;
-  uint16_t* resid;
-  float* ss_out;
-  int* counters;
-  int T;
-  int k;
-};
-int moe_gemm_m64g(const uint16_t*, const int32_t*, const int32_t*, int, int, const uint16_t*, int, int, float*,
-                  uint16_t*, int, int, int, int, int, hipStream_t, const int32_t*, const MoeResidEpi* = nullptr,
-                  int pairs = 0);
 void add_partials_rmsnorm(const float*, int, int, uint16_t*, const uint16_t*, uint16_t*, int, float, hipStream_t);
 void reduce_partials(const float*, int, int64_t, uint16_t*, hipStream_t);
 int rope_cache_partials(const float*, int, uint16_t*, int64_t, const int32_t*, const float*, uint16_t*, uint16_t*,
@@ -70,8 +53,6 @@ void sample_tokens(const void*, int, int64_t, int, int, const float*, const floa
 size_t sample_ws_row_bytes();
 void segment_sum(const uint16_t*, int, const int32_t*, const int32_t*, float*, int, hipStream_t);
 void subst_tokens(int32_t*, const int32_t*, const int32_t*, int, hipStream_t);
-int gemm_w8(const uint16_t*, int, int, const uint8_t*, const float*, int, float*, uint16_t*, int, int, int,
-            hipStream_t, int);
 int dequant_w8(const uint8_t*, const float*, int, int, uint16_t*, int, hipStream_t);
 void moe_topk_softmax(const void*, int, int, int, int, int, float*, int32_t*, hipStream_t);
 void moe_align(const int32_t*, int, int, int, int, int, int32_t*, int32_t*, int32_t*, hipStream_t);

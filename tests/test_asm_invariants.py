@@ -8,8 +8,8 @@ matches the issue order) the kernels. This test compiles them and checks:
   * no "reserved registers on the clobber list" warning (M0 goes in as a "{m0}"
     operand, not a clobber);
   * every vmcnt wait in each instantiation is one the pipeline's issue order allows
-    (gemm_mw: the ring formula of gemm_mw.hip; gemm_m64g: G = x + W instructions per
-    chunk, or 0);
+    (gemm_mw: the ring formula of gemm_mw.hip; gemm_m64g, dense and grouped, and
+    gemm_w8: G = x + W instructions per chunk of csrc/kernels/m64_pipe.h, or 0);
   * no VGPR / SGPR spills.
 """
 from __future__ import annotations
@@ -199,6 +199,19 @@ def test_gemm_m64g_waits_are_counted(tmp_path):
             got = _vmcnts(_without_epilogue_blocks(body if MT == 1 else _pipeline(body)))
             assert not {v for v in got if G <= v <= (NS - 2) * G} - counted, (name, sorted(got), sorted(counted))
         assert counted <= got, (name, sorted(got), sorted(counted))
+    # the grouped (MoE) kernels: one kernel holds the row bodies MT in {1, 2, 4, 8} up to its
+    # MT_MAX that stage at least one x DMA per wave; every wait in their pipelines is one of
+    # those bodies' counted G, or the drain
+    gs = _kernels(asm, "_ZN3xgk24gemm_m64g_grouped_kernel")
+    assert len(gs) >= 32, len(gs)
+    for name, body in gs.items():
+        NW, WV, KC, _nt, MT_MAX = _targs(name)
+        RPI = 1024 // (KC * 2)
+        counted = {16 * MT // RPI // WV + 16 * NW // RPI
+                   for MT in (1, 2, 4, 8) if MT <= MT_MAX and 16 * MT // RPI // WV >= 1}
+        got = _vmcnts(_without_epilogue_blocks(_pipeline(body)))
+        assert got <= {0} | counted, (name, sorted(got), sorted(counted))
+        assert got & counted, (name, sorted(got), sorted(counted))
     _no_spills(asm)
 
 

@@ -7,6 +7,7 @@ import torch
 
 from ._native import kernels, stream_ptr, use_native
 from .activation import silu_and_mul
+from .linear import M64G_CFGS
 
 BLOCK_M = 64
 # gemm_m64g launch configurations for the expert GEMMs (see ops/linear.py M64G_CFGS);
@@ -22,8 +23,8 @@ MOE_CFG_W2 = 1
 # removed.
 MOE_PREFILL_PAIRS = 256
 MOE_CFG_W2_PREFILL = 3
-# waves per workgroup of each gemm_m64g cfg (csrc/kernels/gemm_m64g.hip m64g_cfg_waves)
-M64G_CFG_WAVES = {0: 4, 1: 4, 2: 4, 3: 4, 4: 2, 5: 2, 6: 2, 7: 8}
+# waves per workgroup of each gemm_m64g cfg
+M64G_CFG_WAVES = {cfg: waves for cfg, (waves, _kc, _nt) in M64G_CFGS.items()}
 MOE_CFG_W13_PREFILL = 3
 # prefill-sized steps on gemm_pf's grouped form instead (csrc/kernels/gemm_pf.hip
 # gemm_pf_grouped): one MFMA tile of 192-288 rows covers an expert's rows, so each
