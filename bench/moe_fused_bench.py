@@ -89,7 +89,7 @@ def main():
         res2 = []
         for nw in (1, 2):
             for cfg in range(7):
-                cols = 16 * nw * MO.M64G_CFG_WAVES[cfg]
+                cols = 16 * nw * MO.M64G_CFGS[cfg][0]
                 if H % cols or H // cols > 64:
                     continue
                 for S in (1, 2, 4, 8):

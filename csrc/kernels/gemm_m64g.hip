@@ -24,7 +24,8 @@
 #include <algorithm>
 
 #include "m64_pipe.h"
-#include "m64g_api.h"
+#include "cfg_dispatch.h"
+#include "gemm_api.h"
 #include "../comm/ll.h"
 
 namespace xgk {
@@ -788,8 +789,7 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_grouped_kernel(const uin
     const int real = __syncthreads_count(t < 64 && rt0 + t < p1 && valid[rt0 + t] >= 0);
     amt = (real + 15) / 16;
   }
-  constexpr int RPI = 1024 / (KC * 2);
-  constexpr bool MT1_OK = (16 / RPI / WV) >= 1;  // one 16-row x sub-tile is >= one DMA per wave
+  constexpr bool MT1_OK = m64_x_dmas(WV, KC, 1) >= 1;  // one 16-row x sub-tile is >= one DMA per wave
   if constexpr (MT_MAX >= 4) {
     if (amt > 2) {
       grouped_body<NW, WV, KC, NT, 4>(x, rows, e, p0, p1, rt0, K, w, N, P, part, out, mode, lds0, lds1, lds2, krot, mre, contributors);
@@ -806,49 +806,55 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_m64g_grouped_kernel(const uin
     grouped_body<NW, WV, KC, NT, 1>(x, rows, e, p0, p1, rt0, K, w, N, P, part, out, mode, lds0, lds1, lds2, krot, mre, contributors);
 }
 
-template <int NW>
-static void launch_m64g_grouped(int cfg, dim3 grid, hipStream_t st, const uint16_t* x, const int32_t* rows,
-                                const int32_t* offs, const int32_t* valid, int E, int K, const uint16_t* w, int N,
-                                int P, float* part, uint16_t* out, int mode, bool mt1, bool mt8,
-                                const MoeResidEpi& mre) {
-#define XGK_GRP_MT(WV, KC, NT, MT)                                                                              \
-  hipLaunchKernelGGL((gemm_m64g_grouped_kernel<NW, WV, KC, NT, MT>), grid, dim3(64 * WV), 0, st, x, rows, offs, \
-                     valid, E, K, w, N, P, part, out, mode, k_rotation(static_cast<int>(grid.y)), mre)
-#define XGK_GRP(WV, KC, NT)              \
-  do {                                   \
-    if (mt1) XGK_GRP_MT(WV, KC, NT, 1);  \
-    else XGK_GRP_MT(WV, KC, NT, 4);      \
-  } while (0)
-  // 128-row pairs (KC 64 configs only: the x slot doubles)
-#define XGK_GRP8(WV, KC, NT)                 \
-  do {                                       \
-    if (mt8) XGK_GRP_MT(WV, KC, NT, 8);      \
-    else if (mt1) XGK_GRP_MT(WV, KC, NT, 1); \
-    else XGK_GRP_MT(WV, KC, NT, 4);          \
-  } while (0)
-  // the 4-wave KC-64 configs have < 1 x DMA instruction per wave at 16 rows: MT >= 2
-  switch (cfg) {
-    case 1: XGK_GRP(4, 128, true); break;
-    case 2:
-      if (mt8) XGK_GRP_MT(4, 64, false, 8);
-      else XGK_GRP_MT(4, 64, false, 4);
-      break;
-    case 3:
-      if (mt8) XGK_GRP_MT(4, 64, true, 8);
-      else XGK_GRP_MT(4, 64, true, 4);
-      break;
-    case 4: XGK_GRP8(2, 64, false); break;
-    case 5: XGK_GRP8(2, 64, true); break;
-    case 6: XGK_GRP(2, 128, true); break;
-    default: XGK_GRP(4, 128, false); break;
-  }
-#undef XGK_GRP
-#undef XGK_GRP8
-#undef XGK_GRP_MT
+// The launch configurations, indexed by cfg. Which kernels a row has follows from it:
+// the one-x-tile kernel (MT 1: M, or every expert's rows, <= 16) iff a 16-row x tile is
+// at least one DMA instruction per wave; the four-x-tile kernel iff the ring has 3 slots
+// (the deeper rings hold more weight bytes in flight per CU instead); grouped, the
+// 128-row pair kernel (MT_MAX 8) iff kc == 64 (the x slot doubles).
+constexpr M64Cfg M64_CFGS[] = {
+    // waves, kc, nt, ring slots, grouped
+    {4, 128, false, 3, true}, {4, 128, true, 3, true},   {4, 64, false, 3, true}, {4, 64, true, 3, true},
+    {2, 64, false, 3, true},  {2, 64, true, 3, true},    {2, 128, true, 3, true}, {8, 64, true, 3, false},
+    {2, 128, true, 5, false}, {4, 128, true, 4, false},  {2, 64, true, 6, false}};
+constexpr int M64_NCFG = table_size(M64_CFGS);
+constexpr bool m64_has_mt1(const M64Cfg& c) { return m64_x_dmas(c.wv, c.kc, 1) >= 1; }
+constexpr bool m64_has_mt4(const M64Cfg& c) { return c.ns == 3; }
+int m64g_cfgs(const M64Cfg** rows) {
+  *rows = M64_CFGS;
+  return M64_NCFG;
 }
 
-int m64g_cfg_waves(int cfg);
-int m64g_cfg_kc(int cfg);
+template <int NW, int C>
+static void launch_m64g_grouped(dim3 grid, hipStream_t st, const uint16_t* x, const int32_t* rows,
+                                const int32_t* offs, const int32_t* valid, int E, int K, const uint16_t* w, int N,
+                                int P, float* part, uint16_t* out, int mode, int max_rows, const MoeResidEpi& mre) {
+  static constexpr M64Cfg c = M64_CFGS[C];
+  auto go = [&](auto mt) {
+    hipLaunchKernelGGL((gemm_m64g_grouped_kernel<NW, c.wv, c.kc, c.nt, decltype(mt)::value>), grid, dim3(64 * c.wv), 0,
+                       st, x, rows, offs, valid, E, K, w, N, P, part, out, mode,
+                       k_rotation(static_cast<int>(grid.y)), mre);
+  };
+  // 128-row pairs for prefill-sized steps (> 256 pairs; decode keeps the 48 KB-slot
+  // kernel and its occupancy)
+  if constexpr (c.kc == 64) {
+    if (max_rows > 256) return go(Int<8>{});
+  }
+  if constexpr (m64_has_mt1(c)) {
+    if (max_rows <= 16) return go(Int<1>{});
+  }
+  go(Int<4>{});
+}
+
+bool moe_m64g_supports(int E, int K, int N, int P, int S, int mode, int nw, int cfg, int max_rows) {
+  if (E < 1 || P < 0 || P % 64 || S < 1 || (nw != 1 && nw != 2) || cfg < 0 || cfg >= M64_NCFG) return false;
+  const M64Cfg& c = M64_CFGS[cfg];
+  if (!c.grouped) return false;
+  if (mode != GG_BF16 && mode != GG_PARTIAL && mode != GG_SILU && mode != GG_MOE_RESID) return false;
+  // GG_MOE_RESID: decode-sized steps; the next norm sums <= 64 partial sums per row
+  if (mode == GG_MOE_RESID && (max_rows > 256 || N / c.cols(nw) > 64)) return false;
+  if (K % (S * c.kc) || N % c.cols(nw)) return false;
+  return !(mode == GG_SILU && (nw != 2 || S != 1));
+}
 
 // max_rows: a bound on the real rows of any expert (<= 16 selects the one-x-tile
 // kernel; rows 16..63 of each padded tile are then left unwritten -- pads only).
@@ -861,92 +867,61 @@ int m64g_cfg_kc(int cfg);
 int moe_gemm_m64g(const uint16_t* x, const int32_t* rows, const int32_t* offs, int E, int K, const uint16_t* w, int N,
                   int P, float* part, uint16_t* out, int S, int mode, int nw, int cfg, int max_rows, hipStream_t st,
                   const int32_t* valid, const MoeResidEpi* mre_in, int pairs) {
-  if (E < 1 || P < 0 || P % 64 || S < 1 || (nw != 1 && nw != 2) || cfg < 0 || cfg > 6) return 1;
-  if (mode != GG_BF16 && mode != GG_PARTIAL && mode != GG_SILU && mode != GG_MOE_RESID) return 1;
+  if (!moe_m64g_supports(E, K, N, P, S, mode, nw, cfg, max_rows)) return 1;
   const MoeResidEpi mre = mre_in ? *mre_in : MoeResidEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
   if (mode == GG_MOE_RESID && (mre.dest == nullptr || mre.w == nullptr || mre.resid == nullptr ||
-                               mre.ss_out == nullptr || mre.counters == nullptr || mre.T < 1 || mre.k < 1 ||
-                               max_rows > 256 || (16 * nw * m64g_cfg_waves(cfg)) % 4 ||
-                               N / (16 * nw * m64g_cfg_waves(cfg)) > 64))  // the next norm sums <= 64 per row
+                               mre.ss_out == nullptr || mre.counters == nullptr || mre.T < 1 || mre.k < 1))
     return 1;
-  const int cols = 16 * nw * m64g_cfg_waves(cfg), kc = m64g_cfg_kc(cfg);
-  if (K % (S * kc) || N % cols) return 1;
-  if (mode == GG_SILU && (nw != 2 || S != 1)) return 1;
   if ((mode == GG_PARTIAL || mode == GG_MOE_RESID) && part == nullptr) return 1;
   if (mode != GG_PARTIAL && mode != GG_MOE_RESID && out == nullptr) return 1;
   if (P == 0) return 0;
   const int ztiles = pairs > 0 ? std::min(P / 64, (pairs + 63) / 64 + std::min(E, pairs)) : P / 64;
-  const dim3 grid(N / cols, S, ztiles);
-  const bool mt1 = max_rows <= 16 && cfg != 2 && cfg != 3;  // 16 x rows >= one DMA per wave
-  // 128-row pairs for prefill-sized steps (> 256 pairs; decode keeps the 48 KB-slot
-  // kernel and its occupancy), KC 64 configs only
-  const bool mt8 = max_rows > 256 && m64g_cfg_kc(cfg) == 64;
-  if (nw == 1) launch_m64g_grouped<1>(cfg, grid, st, x, rows, offs, valid, E, K, w, N, P, part, out, mode, mt1, mt8, mre);
-  else launch_m64g_grouped<2>(cfg, grid, st, x, rows, offs, valid, E, K, w, N, P, part, out, mode, mt1, mt8, mre);
+  const dim3 grid(N / M64_CFGS[cfg].cols(nw), S, ztiles);
+  cfg_dispatch<M64_NCFG>(cfg, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    if constexpr (M64_CFGS[C].grouped) {
+      if (nw == 1)
+        launch_m64g_grouped<1, C>(grid, st, x, rows, offs, valid, E, K, w, N, P, part, out, mode, max_rows, mre);
+      else
+        launch_m64g_grouped<2, C>(grid, st, x, rows, offs, valid, E, K, w, N, P, part, out, mode, max_rows, mre);
+    }
+  });
   return 0;
 }
 
-// cfg: 0 = (4 waves, KC 128), 1 = (4, 128, nt), 2 = (4, 64), 3 = (4, 64, nt),
-//      4 = (2, 64), 5 = (2, 64, nt), 6 = (2, 128, nt), 7 = (8, 64, nt; four x tiles only:
-//      a 16-row x tile is less than one DMA instruction per wave at 8 waves)
-template <int NW>
-static void launch_m64g(int cfg, dim3 grid, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N,
+template <int NW, int C>
+static void launch_m64g(dim3 grid, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N,
                         float* part, uint16_t* out, int mode, const M64Epi& epi) {
-  // M <= 16: the one-x-tile kernel, except the 4-wave KC-64 configs (16 x rows would
-  // be less than one DMA instruction per wave)
-  const bool mt1 = M <= 16 && cfg != 2 && cfg != 3;
-#define XGK_M64G(WV, KC, NT)                                                                                         \
-  do {                                                                                                               \
-    if (mt1)                                                                                                         \
-      hipLaunchKernelGGL((gemm_m64g_kernel<NW, WV, KC, NT, 1>), grid, dim3(64 * WV), 0, st, x, M, K, w, N, part, out, \
-                         mode, epi);                                                                                 \
-    else                                                                                                             \
-      hipLaunchKernelGGL((gemm_m64g_kernel<NW, WV, KC, NT, 4>), grid, dim3(64 * WV), 0, st, x, M, K, w, N, part, out, \
-                         mode, epi);                                                                                 \
-  } while (0)
-#define XGK_M64G4(WV, KC, NT)                                                                                      \
-  hipLaunchKernelGGL((gemm_m64g_kernel<NW, WV, KC, NT, 4>), grid, dim3(64 * WV), 0, st, x, M, K, w, N, part, out, \
-                     mode, epi)
-// deep-ring one-x-tile configurations (M <= 16 only)
-#define XGK_M64G_DEEP(WV, KC, NT, NSV)                                                                             \
-  hipLaunchKernelGGL((gemm_m64g_kernel<NW, WV, KC, NT, 1, NSV>), grid, dim3(64 * WV), 0, st, x, M, K, w, N, part, \
-                     out, mode, epi)
-  switch (cfg) {
-    case 1: XGK_M64G(4, 128, true); break;
-    case 2: XGK_M64G4(4, 64, false); break;
-    case 3: XGK_M64G4(4, 64, true); break;
-    case 4: XGK_M64G(2, 64, false); break;
-    case 5: XGK_M64G(2, 64, true); break;
-    case 6: XGK_M64G(2, 128, true); break;
-    case 7: XGK_M64G4(8, 64, true); break;
-    case 8: XGK_M64G_DEEP(2, 128, true, 5); break;
-    case 9: XGK_M64G_DEEP(4, 128, true, 4); break;
-    case 10: XGK_M64G_DEEP(2, 64, true, 6); break;
-    default: XGK_M64G(4, 128, false); break;
+  static constexpr M64Cfg c = M64_CFGS[C];
+  static_assert(m64_has_mt1(c) || m64_has_mt4(c), "a cfg without a kernel");
+  auto go = [&](auto mt) {
+    hipLaunchKernelGGL((gemm_m64g_kernel<NW, c.wv, c.kc, c.nt, decltype(mt)::value, c.ns>), grid, dim3(64 * c.wv), 0,
+                       st, x, M, K, w, N, part, out, mode, epi);
+  };
+  if constexpr (m64_has_mt1(c)) {
+    if (M <= 16 || !m64_has_mt4(c)) return go(Int<1>{});
   }
-#undef XGK_M64G
-#undef XGK_M64G4
-#undef XGK_M64G_DEEP
+  if constexpr (m64_has_mt4(c)) go(Int<4>{});
 }
 
-int m64g_cfg_waves(int cfg) { return cfg == 7 ? 8 : cfg == 9 ? 4 : (cfg >= 4 ? 2 : 4); }
-int m64g_cfg_kc(int cfg) {
-  return (cfg == 2 || cfg == 3 || cfg == 4 || cfg == 5 || cfg == 7 || cfg == 10) ? 64 : 128;
+bool m64g_supports(int M, int K, int N, int S, int mode, int nw, int cfg) {
+  if (M < 1 || M > M64G_MAX_M || S < 1 || (nw != 1 && nw != 2) || cfg < 0 || cfg >= M64_NCFG) return false;
+  const M64Cfg& c = M64_CFGS[cfg];
+  if (M > 16 && !m64_has_mt4(c)) return false;  // deep-ring configurations: one x tile only
+  if (mode < GG_BF16 || mode > GG_AR || mode == GG_MOE_RESID) return false;
+  if (K % c.kc || S > K / c.kc || N % c.cols(nw)) return false;  // (uneven split-K ranges are fine)
+  // split-K SiLU reduces its slabs in the GEMM's tail (m64g_silu_tail): gate / up pairs only
+  return !(mode == GG_SILU && nw != 2) && !(mode == GG_BF16 && S != 1);
 }
 
-// Host-side shape / operand checks shared by both entry points (0 = valid).
+// Host-side shape / operand checks shared by the entry points (0 = valid).
 static int m64g_check(int M, int K, int N, const float* part, const uint16_t* out, int S, int mode, int nw, int cfg,
                       const M64Epi& epi) {
-  if (M < 1 || M > 64 || S < 1 || (nw != 1 && nw != 2) || cfg < 0 || cfg > 10) return 1;
-  if (cfg >= 8 && M > 16) return 1;  // deep-ring configurations: one x tile only
-  if (mode < GG_BF16 || mode > GG_AR || mode == GG_MOE_RESID) return 1;
+  if (!m64g_supports(M, K, N, S, mode, nw, cfg)) return 1;
   // the consumer's statistics paths sum at most 64 partial sums per row, 128 at M <= 16
   if (epi.ss_in != nullptr && (epi.ss_n < 1 || epi.ss_n > (M <= 16 ? 128 : 64) || epi.ss_stride < M)) return 1;
-  const int cols = 16 * nw * m64g_cfg_waves(cfg), kc = m64g_cfg_kc(cfg);
-  if (K % kc || S > K / kc || N % cols) return 1;
   // split-K SiLU: fp32 slabs + one zeroed arrival ticket per column tile (m64g_silu_tail)
-  if (mode == GG_SILU && (nw != 2 || (S > 1 && (part == nullptr || epi.counters == nullptr)))) return 1;
-  if (mode == GG_BF16 && S != 1) return 1;
+  if (mode == GG_SILU && S > 1 && (part == nullptr || epi.counters == nullptr)) return 1;
   if ((mode == GG_PARTIAL || mode == GG_RESID || mode == GG_AR) && part == nullptr) return 1;
   if ((mode == GG_BF16 || mode == GG_SILU) && out == nullptr) return 1;
   if ((mode == GG_RESID || mode == GG_AR) && (epi.resid == nullptr || epi.ss_out == nullptr || epi.counters == nullptr))
@@ -957,12 +932,14 @@ static int m64g_check(int M, int K, int N, const float* part, const uint16_t* ou
 
 static void m64g_launch(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S,
                         int mode, int nw, int cfg, const M64Epi& epi_in, hipStream_t st) {
-  const int tiles = N / (16 * nw * m64g_cfg_waves(cfg));
   M64Epi epi = epi_in;
   epi.krot = k_rotation(S);
-  const dim3 grid(tiles, S);
-  if (nw == 1) launch_m64g<1>(cfg, grid, st, x, M, K, w, N, part, out, mode, epi);
-  else launch_m64g<2>(cfg, grid, st, x, M, K, w, N, part, out, mode, epi);
+  const dim3 grid(N / M64_CFGS[cfg].cols(nw), S);
+  cfg_dispatch<M64_NCFG>(cfg, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    if (nw == 1) launch_m64g<1, C>(grid, st, x, M, K, w, N, part, out, mode, epi);
+    else launch_m64g<2, C>(grid, st, x, M, K, w, N, part, out, mode, epi);
+  });
 }
 
 int gemm_m64g(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S, int mode,

@@ -33,13 +33,19 @@
 //     M = 256, more than one 4 MB L2).
 // Epilogues: fp32 partials, bf16, or the SiLU gate of a block-16 interleaved
 // gate|up weight (split 1).
+#include "cfg_dispatch.h"
+#include "gemm_api.h"
 #include "glds.h"
 
 namespace xgk {
 
-int k_rotation(int S);  // gemm_m64g.hip
-
 enum : int { MW_BF16 = 0, MW_PARTIAL = 1, MW_SILU = 2 };
+
+// LDS of a workgroup: D + 1 weight slots of 16 WN NWT rows and D x slots of
+// 16 (8 / WN) MTW rows, 128 B (64 k) per row.
+constexpr int mw_lds_bytes(int wn, int nwt, int mtw, int d) {
+  return (d + 1) * (wn * 16 * nwt * 128) + d * ((8 / wn) * 16 * mtw * 128);
+}
 
 // PR: anatomy-probe code paths of round 4 (profiles/r4_mw_probe.md), now always 0:
 // PR & 7 selects compiled-out pipeline parts, PR & 8 forces K rotation.
@@ -58,7 +64,8 @@ __global__ void __launch_bounds__(512, 1) gemm_mw_kernel(const uint16_t* __restr
   constexpr int XI = XROWS / RPI / 8;           // x DMA instructions per wave per chunk
   static_assert(WN * WM == 8 && WI >= 1 && XI >= 1 && WCOLS % 64 == 0 && XROWS % 64 == 0, "bad gemm_mw geometry");
   static_assert(D >= 2 && D <= 4, "ring depth");
-  static_assert((D + 1) * WSLOT + D * XSLOT <= 160 * 1024, "LDS");
+  static_assert((D + 1) * WSLOT + D * XSLOT == mw_lds_bytes(WN, NWT, MTW, D) &&
+                    mw_lds_bytes(WN, NWT, MTW, D) <= LDS_BYTES, "LDS");
   // ONE __shared__ object (cdna_hip_programming.md §5 "Three .s-level traps" (a))
   __shared__ __attribute__((aligned(1024))) uint8_t smem[(D + 1) * WSLOT + D * XSLOT];
   uint8_t* const wring = smem;
@@ -233,50 +240,34 @@ __global__ void __launch_bounds__(512, 1) gemm_mw_kernel(const uint16_t* __restr
 // chunk c's MFMAs; r4_mw_sweep_v1.jsonl) never beat the kernel above on a default plan,
 // and the anatomy probes (PR != 0, r4_mw_probe.md) were measurement builds.)
 
-// cfg -> (WN, NWT, D, NT): 0 = 4 x 2 waves, 256 columns, ring 2, nt weights;
-// 1 = 4 x 2, 128 columns, ring 3, nt; 2 = 4 x 2, 128 columns, ring 2, nt; 3 / 4 = 0 / 1
-// with default-policy weight loads; 5 = 2 x 4 waves, 128 columns, ring 3, nt;
-// 6 = 2 x 4 waves, 256 columns, ring 2, nt. The x tile follows M: 32-row steps on the
-// 4 x 2 layouts (64 .. 320 rows), 64-row steps on the 2 x 4 ones (64 .. 256).
-int mw_cfg_cols(int cfg) { return (cfg == 0 || cfg == 3 || cfg == 6) ? 256 : 128; }
-static int mw_cfg_wn(int cfg) { return cfg >= 5 ? 2 : 4; }
-
-template <int WN, int NWT, int MTW, int D>
-constexpr bool mw_fits() {
-  constexpr int WM = 8 / WN;
-  return (WM * 16 * MTW) % 64 == 0 && (D + 1) * (WN * 16 * NWT * 128) + D * (WM * 16 * MTW * 128) <= 160 * 1024;
+// The launch configurations, indexed by cfg: (WN, NWT, ring depth, nt weight loads).
+// 0-4: 4 x 2 waves as N x M (0 / 3: 256 columns, 1 / 2 / 4: 128), 5-6: 2 x 4 waves (fewer
+// LDS fragment reads per MFMA). The x tile follows M in 64-row steps, as far as the LDS
+// holds it next to the row's rings (mw_fits): 320 rows on cfg 2 only, 256 on the others.
+constexpr MwCfg MW_CFGS[] = {{4, 4, 2, true},  {4, 2, 3, true}, {4, 2, 2, true}, {4, 4, 2, false},
+                             {4, 2, 3, false}, {2, 4, 3, true}, {2, 8, 2, true}};
+constexpr int MW_NCFG = table_size(MW_CFGS);
+constexpr int MW_MAX_XT = MW_MAX_M / 64;                                     // 64-row x tiles
+constexpr int mw_mtw(const MwCfg& c, int xt) { return 4 * xt / (8 / c.wn); }  // 16-row tiles per wave
+constexpr bool mw_fits(const MwCfg& c, int xt) { return mw_lds_bytes(c.wn, c.nwt, mw_mtw(c, xt), c.d) <= LDS_BYTES; }
+int mw_cfgs(const MwCfg** rows) {
+  *rows = MW_CFGS;
+  return MW_NCFG;
 }
 
-template <int WN, int NWT, int D, bool NT>
-static int launch_mw(int mtw, dim3 grid, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N,
-                     int S, float* part, uint16_t* out, int mode) {
-#define XGK_MW(MTW)                                                                                             \
-  case MTW:                                                                                                     \
-    if constexpr (mw_fits<WN, NWT, MTW, D>()) {                                                                 \
-      hipLaunchKernelGGL((gemm_mw_kernel<WN, NWT, MTW, D, NT>), grid, dim3(512), 0, st, x, M, K, w, N, S, part, \
-                         out, mode, k_rotation(S));                                                             \
-      return 0;                                                                                                 \
-    }                                                                                                           \
-    return 1;
-  if constexpr (WN == 4) {
-    switch (mtw) {
-      XGK_MW(2)
-      XGK_MW(4)
-      XGK_MW(6)
-      XGK_MW(8)
-      XGK_MW(10)
-      default: return 1;
-    }
-  } else {
-    switch (mtw) {
-      XGK_MW(1)
-      XGK_MW(2)
-      XGK_MW(3)
-      XGK_MW(4)
-      default: return 1;
-    }
-  }
-#undef XGK_MW
+template <int C, int XT>
+static void launch_mw(dim3 grid, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N, int S,
+                      float* part, uint16_t* out, int mode) {
+  static constexpr MwCfg c = MW_CFGS[C];
+  if constexpr (mw_fits(c, XT))
+    hipLaunchKernelGGL((gemm_mw_kernel<c.wn, c.nwt, mw_mtw(c, XT), c.d, c.nt>), grid, dim3(512), 0, st, x, M, K, w, N,
+                       S, part, out, mode, k_rotation(S));
+}
+
+bool mw_supports(int M, int K, int N, int S, int mode, int cfg) {
+  if (M < 1 || M > MW_MAX_M || cfg < 0 || cfg >= MW_NCFG || S < 1 || K % 64 || S > K / 64) return false;
+  if (N % MW_CFGS[cfg].cols() || !mw_fits(MW_CFGS[cfg], (M + 63) / 64)) return false;
+  return mode == MW_PARTIAL || ((mode == MW_BF16 || mode == MW_SILU) && S == 1);
 }
 
 // x [M, K] bf16 row-major, w [N, K] bf16 row-major. mode MW_PARTIAL: part [S, M, N]
@@ -284,29 +275,15 @@ static int launch_mw(int mtw, dim3 grid, hipStream_t st, const uint16_t* x, int 
 // shape / configuration this kernel does not take (M beyond the cfg's LDS budget).
 int gemm_mw(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S, int mode,
             int cfg, hipStream_t st) {
-  if (M < 1 || M > 320 || cfg < 0 || cfg >= 7 || S < 1 || K % 64 || S > K / 64) return 1;
-  const int cols = mw_cfg_cols(cfg);
-  if (N % cols) return 1;
-  if (mode == MW_PARTIAL) {
-    if (part == nullptr) return 1;
-  } else if (mode == MW_BF16 || mode == MW_SILU) {
-    if (out == nullptr || S != 1) return 1;
-  } else {
-    return 1;
-  }
-  const dim3 grid((N / cols) * S);
-  int mtw;
-  if (mw_cfg_wn(cfg) == 4) mtw = M <= 64 ? 2 : M <= 128 ? 4 : M <= 192 ? 6 : M <= 256 ? 8 : 10;
-  else mtw = (M + 63) / 64;
-  switch (cfg) {
-    case 0: return launch_mw<4, 4, 2, true>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-    case 1: return launch_mw<4, 2, 3, true>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-    case 2: return launch_mw<4, 2, 2, true>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-    case 3: return launch_mw<4, 4, 2, false>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-    case 4: return launch_mw<4, 2, 3, false>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-    case 5: return launch_mw<2, 4, 3, true>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-    default: return launch_mw<2, 8, 2, true>(mtw, grid, st, x, M, K, w, N, S, part, out, mode);
-  }
+  if (!mw_supports(M, K, N, S, mode, cfg)) return 1;
+  if (mode == MW_PARTIAL ? part == nullptr : out == nullptr) return 1;
+  const dim3 grid((N / MW_CFGS[cfg].cols()) * S);
+  cfg_dispatch<MW_NCFG>(cfg, [&](auto c) {
+    cfg_dispatch<MW_MAX_XT>((M - 1) / 64, [&](auto xt) {
+      launch_mw<decltype(c)::value, decltype(xt)::value + 1>(grid, st, x, M, K, w, N, S, part, out, mode);
+    });
+  });
+  return 0;
 }
 
 }  // namespace xgk

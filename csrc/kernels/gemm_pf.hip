@@ -46,11 +46,11 @@
 // weights stream once per step (profiles/r5_moe_pf.md).
 #include <type_traits>
 
+#include "cfg_dispatch.h"
+#include "gemm_api.h"
 #include "glds.h"
 
 namespace xgk {
-
-int k_rotation(int S);  // gemm_m64g.hip
 
 enum : int { PF_BF16 = 0, PF_PARTIAL = 1, PF_SILU = 2 };
 constexpr int PF_GROUP_M = 8;  // M tiles per group of the tile order
@@ -439,106 +439,82 @@ __global__ void __launch_bounds__(512, 1) gemm_pf_kernel(const uint16_t* __restr
   }
 }
 
-template <int BM, int MTP, bool NT, int PR = 0, int LAG = 1>
-static int launch_pf(int tiles, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N, int S,
-                     float* part, uint16_t* out, int mode) {
-  const PfGrp ng{nullptr, nullptr, 0, 0, 0};
-  hipLaunchKernelGGL((gemm_pf_kernel<BM, MTP, NT, PR, LAG>), dim3(tiles * S), dim3(512), 0, st, x, M, K, w, N, S, part,
-                     out, mode, pf_krot, ng);
-  return static_cast<int>(hipGetLastError());
-}
-
-// cfg % 16 -> (BM, MTP): 0 (256, 2)  1 (192, 2)  2 (128, 2)  3 (256, 4)  4 (192, 3)  5 (288, 3);
-// with DMA lag 2 (fragment reads retire after the barrier; 3+ phases only): 6 (288, 3)
-// 7 (256, 2)  8 (192, 2);
+// The launch configurations, indexed by cfg % 16: (BM, MTP, DMA lag, grouped). Lag 2:
+// the fragment reads retire after the barrier. The grouped (MoE) form takes the lag-2
+// rows. W stays on cached DMA (non-temporal measured slower: the M tiles of a W tile
+// re-read it through L2).
 // cfg / 16: 0 the kernel, 1 no DMA, 2 no MFMA (anatomy probes, bench/pf_gemm_bench.py
-// --probe: garbage results). W stays on cached DMA (non-temporal measured slower: the
-// M tiles of a W tile re-read it through L2).
-int pf_cfg_bm(int cfg) {
-  switch (cfg & 15) {
-    case 1: case 4: case 8: return 192;
-    case 2: return 128;
-    case 5: case 6: return 288;
-    default: return 256;
-  }
+// --probe: garbage results; measurement builds only, xgserve/_build.py --probes).
+constexpr PfCfg PF_CFGS[] = {{256, 2, 1, false}, {192, 2, 1, false}, {128, 2, 1, false},
+                             {256, 4, 1, false}, {192, 3, 1, false}, {288, 3, 1, false},
+                             {288, 3, 2, true},  {256, 2, 2, true},  {192, 2, 2, true}};
+constexpr int PF_NCFG = table_size(PF_CFGS);
+#ifdef XGK_PROBES
+constexpr int PF_NPROBE = 3;
+#else
+constexpr int PF_NPROBE = 1;
+#endif
+int pf_cfgs(const PfCfg** rows) {
+  *rows = PF_CFGS;
+  return PF_NCFG;
 }
 
-template <int PR>
-static int launch_pf_cfg(int c, int tiles, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N,
-                         int S, float* part, uint16_t* out, int mode) {
-  switch (c) {
-    case 0: return launch_pf<256, 2, false, PR>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 1: return launch_pf<192, 2, false, PR>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 2: return launch_pf<128, 2, false, PR>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 3: return launch_pf<256, 4, false, PR>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 4: return launch_pf<192, 3, false, PR>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 5: return launch_pf<288, 3, false, PR>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 6: return launch_pf<288, 3, false, PR, 2>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 7: return launch_pf<256, 2, false, PR, 2>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    case 8: return launch_pf<192, 2, false, PR, 2>(tiles, st, x, M, K, w, N, S, part, out, mode);
-    default: return 1;
-  }
-}
-
-// grouped (MoE): data-parallel only, no K rotation
-template <int BM, int MTP, int LAG>
-static int launch_pf_grp(int tiles, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N, int S,
-                         float* part, uint16_t* out, int mode, const PfGrp& grp) {
-  hipLaunchKernelGGL((gemm_pf_kernel<BM, MTP, false, 0, LAG, true>), dim3(tiles * S), dim3(512), 0, st, x, M, K, w, N,
-                     S, part, out, mode, 0, grp);
+// GRP: the grouped (MoE) form -- data-parallel only, no K rotation
+template <int C, int PR, bool GRP>
+static int launch_pf(int tiles, hipStream_t st, const uint16_t* x, int M, int K, const uint16_t* w, int N, int S,
+                     float* part, uint16_t* out, int mode, const PfGrp& grp) {
+  static constexpr PfCfg c = PF_CFGS[C];
+  hipLaunchKernelGGL((gemm_pf_kernel<c.bm, c.mtp, false, PR, c.lag, GRP>), dim3(tiles * S), dim3(512), 0, st, x, M, K,
+                     w, N, S, part, out, mode, GRP ? 0 : pf_krot, grp);
   return static_cast<int>(hipGetLastError());
+}
+
+static bool pf_shape_ok(int K, int N, int S, int mode) {
+  if (K < 64 || K % 64 || N < pf::BN || N % pf::BN || S < 1 || S > K / 64) return false;
+  return mode == PF_PARTIAL || ((mode == PF_BF16 || mode == PF_SILU) && S == 1);
+}
+bool pf_supports(int M, int K, int N, int S, int mode, int cfg) {
+  return M >= 1 && cfg >= 0 && cfg / 16 < PF_NPROBE && cfg % 16 < PF_NCFG && pf_shape_ok(K, N, S, mode);
+}
+bool pf_grouped_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg) {
+  return E >= 1 && P >= 1 && P % 64 == 0 && max_pairs >= 1 && cfg >= 0 && cfg < PF_NCFG && PF_CFGS[cfg].grouped &&
+         pf_shape_ok(K, N, S, mode);
 }
 
 // Grouped (MoE experts, moe_align layout): out / part rows are the P sorted rows; w is
 // [E, N, K]; rows gathers x (nullptr: x is already in sorted order); max_pairs bounds
 // the real rows over all experts (sizes the grid: sum over experts of ceil(segment / BM)
-// <= (max_pairs + 63 E) / BM + E). Lag-2 configs 6 / 7 / 8 only.
+// <= (max_pairs + 63 E) / BM + E).
 int gemm_pf_grouped(const uint16_t* x, const int32_t* rows, const int32_t* offs, int E, int P, int K,
                     const uint16_t* w, int N, int max_pairs, float* part, uint16_t* out, int S, int mode, int cfg,
                     hipStream_t st) {
-  if (E < 1 || P < 1 || P % 64 || max_pairs < 1 || offs == nullptr || K < 64 || K % 64 || N < pf::BN ||
-      N % pf::BN || S < 1 || S > K / 64 || cfg < 6 || cfg > 8)
-    return 1;
-  if (mode == PF_PARTIAL) {
-    if (part == nullptr) return 1;
-  } else if (mode == PF_BF16 || mode == PF_SILU) {
-    if (out == nullptr || S != 1) return 1;
-  } else {
-    return 1;
-  }
-  const int bm = pf_cfg_bm(cfg);
-  const int mt = (max_pairs + 63 * E) / bm + E;
+  if (!pf_grouped_supports(E, P, K, N, max_pairs, S, mode, cfg) || offs == nullptr) return 1;
+  if (mode == PF_PARTIAL ? part == nullptr : out == nullptr) return 1;
+  const int mt = (max_pairs + 63 * E) / PF_CFGS[cfg].bm + E;
   const PfGrp grp{rows, offs, E, mt, static_cast<int64_t>(N) * K};
   const int tiles = mt * (N / pf::BN);
-  switch (cfg) {
-    case 6: return launch_pf_grp<288, 3, 2>(tiles, st, x, P, K, w, N, S, part, out, mode, grp);
-    case 7: return launch_pf_grp<256, 2, 2>(tiles, st, x, P, K, w, N, S, part, out, mode, grp);
-    default: return launch_pf_grp<192, 2, 2>(tiles, st, x, P, K, w, N, S, part, out, mode, grp);
-  }
+  int rc = 1;
+  cfg_dispatch<PF_NCFG>(cfg, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    if constexpr (PF_CFGS[C].grouped) rc = launch_pf<C, 0, true>(tiles, st, x, P, K, w, N, S, part, out, mode, grp);
+  });
+  return rc;
 }
 
 int gemm_pf(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S, int mode,
             int cfg, hipStream_t st) {
-  if (M < 1 || K < 64 || K % 64 || N < pf::BN || N % pf::BN || S < 1 || S > K / 64 || cfg < 0 || cfg >= 48)
-    return 1;
-  if (mode == PF_PARTIAL) {
-    if (part == nullptr) return 1;
-  } else if (mode == PF_BF16 || mode == PF_SILU) {
-    if (out == nullptr || S != 1) return 1;
-  } else {
-    return 1;
-  }
-  const int bm = pf_cfg_bm(cfg);
+  if (!pf_supports(M, K, N, S, mode, cfg)) return 1;
+  if (mode == PF_PARTIAL ? part == nullptr : out == nullptr) return 1;
+  const int bm = PF_CFGS[cfg % 16].bm;
   const int tiles = ((M + bm - 1) / bm) * (N / pf::BN);
-  switch (cfg / 16) {
-    case 0: return launch_pf_cfg<0>(cfg % 16, tiles, st, x, M, K, w, N, S, part, out, mode);
-#ifdef XGK_PROBES  // anatomy probes (no DMA / no MFMA): measurement builds only (xgserve/_build.py --probes)
-    case 1: return launch_pf_cfg<1>(cfg % 16, tiles, st, x, M, K, w, N, S, part, out, mode);
-    default: return launch_pf_cfg<2>(cfg % 16, tiles, st, x, M, K, w, N, S, part, out, mode);
-#else
-    default: return 1;
-#endif
-  }
+  const PfGrp ng{nullptr, nullptr, 0, 0, 0};
+  int rc = 1;
+  cfg_dispatch<PF_NPROBE>(cfg / 16, [&](auto pr) {
+    cfg_dispatch<PF_NCFG>(cfg % 16, [&](auto c) {
+      rc = launch_pf<decltype(c)::value, decltype(pr)::value, false>(tiles, st, x, M, K, w, N, S, part, out, mode, ng);
+    });
+  });
+  return rc;
 }
 
 }  // namespace xgk

@@ -34,14 +34,13 @@
 //            workgroup's scales are staged in LDS before the DMA pipeline starts
 //            (no VGPR-destination global load beside the in-flight LDS-DMA).
 #include "glds.h"
-#include "m64g_api.h"
+#include "cfg_dispatch.h"
+#include "gemm_api.h"
 
 namespace xgk {
 
 enum : int { W8_PARTIAL = 1, W8_SILU = 2 };
 enum : int { WQ_FP8 = 0, WQ_INT8 = 1, WQ_INT4 = 2 };
-constexpr int WQ_GROUP = 128;
-constexpr int WQ_SC_FLOATS = 4096;  // int4 scales staged per workgroup (groups x columns)
 
 // 8 int8 codes (k order) -> bf16x8 A fragment (exact)
 __device__ __forceinline__ bf16x8_t int8x8_to_bf16(uint2 v) {
@@ -290,53 +289,54 @@ __global__ void __launch_bounds__(64 * WV, 1) gemm_w8_kernel(const uint16_t* __r
   }
 }
 
-// cfg: 0 = (NW 2, 4 waves, KC 128), 1 = (2, 2, 128), 2 = (1, 4, 128), 3 = (2, 2, 256), 4 = (2, 4, 256)
-static int w8_cfg_cols(int cfg) {
-  switch (cfg) {
-    case 0: return 128;
-    case 1: return 64;
-    case 2: return 64;
-    case 3: return 64;
-    case 4: return 128;
-    default: return 0;
-  }
+// The launch configurations, indexed by cfg: (NW, waves, KC). Every row has the one-x-tile
+// kernel (M <= 16); the KC 128 rows also the four-x-tile kernel (16 < M <= 64; at KC 256
+// four x tiles are a 32 KB x slot, past the LDS on the 4-wave row).
+constexpr W8Cfg W8_CFGS[] = {{2, 4, 128}, {2, 2, 128}, {1, 4, 128}, {2, 2, 256}, {2, 4, 256}};
+constexpr int W8_NCFG = table_size(W8_CFGS);
+constexpr bool w8_has_mt4(const W8Cfg& c) { return c.kc == 128; }
+int w8_cfgs(const W8Cfg** rows) {
+  *rows = W8_CFGS;
+  return W8_NCFG;
 }
-static int w8_cfg_kc(int cfg) { return cfg >= 3 ? 256 : 128; }
-static int w8_cfg_nw(int cfg) { return cfg == 2 ? 1 : 2; }
 
-template <int FMT>
-static void launch_w8(int cfg, bool mt1, dim3 grid, hipStream_t st, const uint16_t* x, int M, int K, const uint8_t* w,
-                      const float* scale, int N, float* part, uint16_t* out, int mode) {
-#define XGK_W8(NW, WV, KC, MT)                                                                                 \
-  hipLaunchKernelGGL((gemm_w8_kernel<NW, WV, KC, MT, FMT>), grid, dim3(64 * WV), 0, st, x, M, K, w, scale, N, part, \
-                     out, mode)
-  switch (cfg) {
-    case 0: if (mt1) XGK_W8(2, 4, 128, 1); else XGK_W8(2, 4, 128, 4); break;
-    case 1: if (mt1) XGK_W8(2, 2, 128, 1); else XGK_W8(2, 2, 128, 4); break;
-    case 2: if (mt1) XGK_W8(1, 4, 128, 1); else XGK_W8(1, 4, 128, 4); break;
-    case 3: XGK_W8(2, 2, 256, 1); break;
-    default: XGK_W8(2, 4, 256, 1); break;
+template <int FMT, int C>
+static void launch_w8(dim3 grid, hipStream_t st, const uint16_t* x, int M, int K, const uint8_t* w, const float* scale,
+                      int N, float* part, uint16_t* out, int mode) {
+  static constexpr W8Cfg c = W8_CFGS[C];
+  auto go = [&](auto mt) {
+    hipLaunchKernelGGL((gemm_w8_kernel<c.nw, c.wv, c.kc, decltype(mt)::value, FMT>), grid, dim3(64 * c.wv), 0, st, x, M,
+                       K, w, scale, N, part, out, mode);
+  };
+  if constexpr (w8_has_mt4(c)) {
+    if (M > 16) return go(Int<4>{});
   }
-#undef XGK_W8
+  go(Int<1>{});
+}
+
+bool w8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt) {
+  if (M < 1 || M > W8_MAX_M || S < 1 || cfg < 0 || cfg >= W8_NCFG || fmt < WQ_FP8 || fmt > WQ_INT4) return false;
+  const W8Cfg& c = W8_CFGS[cfg];
+  if (M > 16 && !w8_has_mt4(c)) return false;
+  if (mode != W8_PARTIAL && mode != W8_SILU) return false;
+  if (N % c.cols() || K % (S * c.kc)) return false;
+  if (mode == W8_SILU && (c.nw != 2 || S != 1)) return false;
+  // int4: whole groups per split, and the workgroup's scales fit its LDS stage
+  return fmt != WQ_INT4 || ((K / S) % WQ_GROUP == 0 && (K / S / WQ_GROUP) * c.cols() <= WQ_SC_FLOATS);
 }
 
 // fmt: WQ_FP8 / WQ_INT8 (scale [N]) or WQ_INT4 (w [N, K / 2] packed, scale [K / 128, N])
 int gemm_w8(const uint16_t* x, int M, int K, const uint8_t* w, const float* scale, int N, float* part,
             uint16_t* out, int S, int mode, int cfg, hipStream_t st, int fmt) {
-  if (M < 1 || M > 64 || S < 1 || cfg < 0 || cfg > 4 || fmt < WQ_FP8 || fmt > WQ_INT4) return 1;
-  if (M > 16 && cfg >= 3) return 1;  // KC 256 with four x tiles exceeds the LDS
-  if (mode != W8_PARTIAL && mode != W8_SILU) return 1;
-  const int cols = w8_cfg_cols(cfg), kc = w8_cfg_kc(cfg);
-  if (N % cols || K % (S * kc)) return 1;
-  if (mode == W8_SILU && (w8_cfg_nw(cfg) != 2 || S != 1 || out == nullptr)) return 1;
-  if (mode == W8_PARTIAL && part == nullptr) return 1;
-  // int4: whole groups per split, and the workgroup's scales fit its LDS stage
-  if (fmt == WQ_INT4 && ((K / S) % WQ_GROUP || (K / S / WQ_GROUP) * cols > WQ_SC_FLOATS)) return 1;
-  const dim3 grid(N / cols, S);
-  const bool mt1 = M <= 16;
-  if (fmt == WQ_FP8) launch_w8<WQ_FP8>(cfg, mt1, grid, st, x, M, K, w, scale, N, part, out, mode);
-  else if (fmt == WQ_INT8) launch_w8<WQ_INT8>(cfg, mt1, grid, st, x, M, K, w, scale, N, part, out, mode);
-  else launch_w8<WQ_INT4>(cfg, mt1, grid, st, x, M, K, w, scale, N, part, out, mode);
+  if (!w8_supports(M, K, N, S, mode, cfg, fmt)) return 1;
+  if (mode == W8_SILU ? out == nullptr : part == nullptr) return 1;
+  const dim3 grid(N / W8_CFGS[cfg].cols(), S);
+  cfg_dispatch<W8_NCFG>(cfg, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    if (fmt == WQ_FP8) launch_w8<WQ_FP8, C>(grid, st, x, M, K, w, scale, N, part, out, mode);
+    else if (fmt == WQ_INT8) launch_w8<WQ_INT8, C>(grid, st, x, M, K, w, scale, N, part, out, mode);
+    else launch_w8<WQ_INT4, C>(grid, st, x, M, K, w, scale, N, part, out, mode);
+  });
   return 0;
 }
 

@@ -21,6 +21,11 @@
 
 namespace xgk {
 
+// x DMA instructions per wave per chunk of a 16 * mt-row x tile (a wave instruction moves
+// 1024 B = 512 / kc bf16 rows). 0: the tile is less than one instruction per wave, and no
+// kernel of that shape exists (the launchers ask this; M64Geom asserts it).
+constexpr int m64_x_dmas(int wv, int kc, int mt) { return 16 * mt / (512 / kc) / wv; }
+
 // Slot geometry. x rows are bf16 (2 KC bytes); weight rows are WRB bytes (2 KC for bf16,
 // KC for 8-bit codes, KC / 2 for 4-bit codes).
 template <int NW, int WV, int KC, int MT, int WRB_ = 2 * KC>
@@ -29,7 +34,7 @@ struct M64Geom {
   static constexpr int XG = XRB / 16, WG = WRB / 16;            // 16-B granules per row
   static constexpr int XRPI = 1024 / XRB, WRPI = 1024 / WRB;    // rows per DMA instruction (64 lanes x 16 B)
   static constexpr int XROWS = 16 * MT, XBYTES = XROWS * XRB;
-  static constexpr int XI = XROWS / XRPI / WV;                  // x DMA instructions per wave per chunk
+  static constexpr int XI = m64_x_dmas(WV, KC, MT);             // x DMA instructions per wave per chunk
   static constexpr int WROWS = 16 * NW, WBYTES = WROWS * WRB;   // weight rows / bytes per wave per slot
   static constexpr int WI = WROWS / WRPI;                       // weight DMA instructions per wave per chunk
   static constexpr int SLOT = XBYTES + WV * WBYTES;

@@ -11,7 +11,7 @@
 #include <cstring>
 #include <pybind11/stl.h>
 
-#include "m64g_api.h"
+#include "gemm_api.h"
 
 namespace py = pybind11;
 
@@ -22,11 +22,6 @@ void layernorm(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, int
 void silu_and_mul(const uint16_t*, uint16_t*, int, int, int, hipStream_t);
 int skinny_gemm(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, hipStream_t);
 int skinny_slab_kmax(int);
-int gemm_mw(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, int, hipStream_t);
-int gemm_pf_grouped(const uint16_t*, const int32_t*, const int32_t*, int, int, int, const uint16_t*, int, int, float*,
-                    uint16_t*, int, int, int, hipStream_t);
-int gemm_pf(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, int, hipStream_t);
-void set_pf_krot(int);
 void add_partials_resid(const float*, int, int, uint16_t*, float*, int, hipStream_t, uint64_t);
 void row_sumsq(const uint16_t*, int, int, float*, hipStream_t);
 void embed_gather(const int32_t*, int, const uint16_t*, int, int, uint16_t*, float*, hipStream_t);
@@ -293,6 +288,43 @@ PYBIND11_MODULE(_kernels, m) {
           "gemm_m64g_ar");
   });
   m.def("m64g_ar_desc_bytes", &xgk::m64g_ar_desc_bytes);
+  // The GEMM families' configuration tables as {family: [row tuple per cfg]}, the constants
+  // and the no-launch shape predicates: what xgserve/ops/linear.py's pure-Python planners
+  // mirror (tests/test_gemm_cfg_tables.py holds the two together).
+  m.def("gemm_cfgs", []() {
+    py::dict d;
+    const xgk::M64Cfg* m64;
+    py::list l64;
+    for (int i = 0, n = xgk::m64g_cfgs(&m64); i < n; ++i)
+      l64.append(py::make_tuple(m64[i].wv, m64[i].kc, m64[i].nt, m64[i].ns, m64[i].grouped));
+    d["m64g"] = l64;
+    const xgk::W8Cfg* w8;
+    py::list lw8;
+    for (int i = 0, n = xgk::w8_cfgs(&w8); i < n; ++i) lw8.append(py::make_tuple(w8[i].nw, w8[i].wv, w8[i].kc));
+    d["w8"] = lw8;
+    const xgk::MwCfg* mw;
+    py::list lmw;
+    for (int i = 0, n = xgk::mw_cfgs(&mw); i < n; ++i)
+      lmw.append(py::make_tuple(mw[i].cols(), mw[i].d, mw[i].nt));
+    d["mw"] = lmw;
+    const xgk::PfCfg* pf;
+    py::list lpf;
+    for (int i = 0, n = xgk::pf_cfgs(&pf); i < n; ++i)
+      lpf.append(py::make_tuple(pf[i].bm, pf[i].mtp, pf[i].lag, pf[i].grouped));
+    d["pf"] = lpf;
+    return d;
+  });
+  m.attr("WQ_GROUP") = xgk::WQ_GROUP;
+  m.attr("WQ_SC_FLOATS") = xgk::WQ_SC_FLOATS;
+  m.attr("M64G_MAX_M") = xgk::M64G_MAX_M;
+  m.attr("W8_MAX_M") = xgk::W8_MAX_M;
+  m.attr("MW_MAX_M") = xgk::MW_MAX_M;
+  m.def("m64g_supports", &xgk::m64g_supports);
+  m.def("moe_m64g_supports", &xgk::moe_m64g_supports);
+  m.def("w8_supports", &xgk::w8_supports);
+  m.def("mw_supports", &xgk::mw_supports);
+  m.def("pf_supports", &xgk::pf_supports);
+  m.def("pf_grouped_supports", &xgk::pf_grouped_supports);
   m.def("add_partials_resid", [](uintptr_t part, int S_, int T, uintptr_t res, uintptr_t ss_part, int H,
                                  uintptr_t st, uint64_t sim_ticks) {
     if (H % 1024) throw std::invalid_argument("add_partials_resid: H % 1024 != 0");

@@ -435,7 +435,8 @@ def test_fused_moe_grouped(T):
     torch.testing.assert_close(out.cpu().float(), ref, atol=2e-2 * ref.std().item(), rtol=2e-2)
 
 
-@pytest.mark.parametrize("T,E,skew,eoff", [(300, 8, 0.0, 0), (575, 8, 6.0, 0), (700, 4, 3.0, 0), (575, 8, 0.0, 4)])
+@pytest.mark.parametrize("T,E,skew,eoff", [(300, 8, 0.0, 0), (575, 8, 6.0, 0), (700, 4, 3.0, 0), (575, 8, 0.0, 4),
+                                          (900, 8, 0.0, 0)])  # (tiles of 192 / 192 / 288 / 288 / 256 rows)
 def test_fused_moe_prefill_on_gemm_pf(T, E, skew, eoff, monkeypatch):
     """Prefill-sized expert GEMMs on gemm_pf's grouped form (> 256 pairs): balanced and
     skewed routing (an expert with several 192-288-row tiles), an EP shard (pairs of

@@ -260,6 +260,37 @@ def test_gemm_m64g_deep_ring_rejects_m_above_16():
                                     1, 8, stream_ptr())
 
 
+@pytest.mark.parametrize("cfg,M", [(7, 16), (7, 17), (8, 16), (9, 16), (10, 16)])
+def test_gemm_m64g_launcher_branches_of_cfg_7_to_10(cfg, M):
+    """Both tile counts per wave on each side of the 16-row switch, for the configurations
+    no other test launches that way: the 8-wave cfg 7 (other tests reach it through tuned
+    plans) and the deep rings with one tile per wave (the deep-ring shapes above all take
+    two). Cfg 0-6 get the same from tests/test_moe_gemm_gpu.py's dense comparison. Two
+    column tiles, four K chunks (the 3-slot ring wraps), one and two K splits."""
+    from xgserve.ops.linear import M64G_CFGS, m64_linear
+    wv, kc = M64G_CFGS[cfg][:2]
+    for nw in (1, 2):
+        N, K = 2 * 16 * nw * wv, 4 * kc
+        x, w = rnd(M, K), rnd(N, K, scale=0.02)
+        for S in (1, 2):
+            pend = m64_linear(x, w, MODE_PARTIAL, split_k=S, nw=nw, cfg=cfg)
+            assert pend.part.shape == (S, M, N)
+            assert rel_err(pend.part.sum(0), x.float() @ w.float().t()) < 1e-5, (nw, S)
+
+
+@pytest.mark.parametrize("M", [64, 193])
+@pytest.mark.parametrize("cfg", list(range(7)))
+def test_gemm_mw_one_and_four_x_tiles(M, cfg):
+    """The x-tile heights the sweeps above leave out per cfg: one 64-row tile and four."""
+    from xgserve.ops.linear import MW_CFGS, mw_linear
+    N, K = 2 * MW_CFGS[cfg][0], 256
+    x, w = rnd(M, K), rnd(N, K, scale=0.02)
+    for S in (1, 2):
+        pend = mw_linear(x, w, MODE_PARTIAL, plan=(S, cfg))
+        assert pend.part.shape == (S, M, N)
+        assert rel_err(pend.part.sum(0), x.float() @ w.float().t()) < 1e-5, (S,)
+
+
 @pytest.mark.parametrize("M", [1, 16, 40, 64])
 @pytest.mark.parametrize("N,K,nw,S,cfg", [(6144, 4096, 2, 5, 3), (6144, 4096, 1, 3, 0), (4096, 14336, 2, 3, 1),
                                           (4096, 14336, 2, 7, 3), (1024, 768, 1, 5, 4)])

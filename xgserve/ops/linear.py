@@ -94,16 +94,22 @@ def skinny_linear(x: torch.Tensor, w: torch.Tensor, split_k: Optional[int] = Non
     return res
 
 
-# gemm_m64g launch configurations (csrc/kernels/gemm_m64g.hip launch_m64g):
-# cfg -> (waves per workgroup, k chunk, non-temporal weight DMA)
-# 8-10: deep LDS rings (5 / 4 / 6 slots) for M <= 16 -- more weight bytes in flight per CU
-M64G_CFGS = {0: (4, 128, False), 1: (4, 128, True), 2: (4, 64, False), 3: (4, 64, True),
-             4: (2, 64, False), 5: (2, 64, True), 6: (2, 128, True), 7: (8, 64, True),
-             8: (2, 128, True), 9: (4, 128, True), 10: (2, 64, True)}
+# gemm_m64g launch configurations, the mirror of csrc/kernels/gemm_m64g.hip M64_CFGS
+# (tests/test_gemm_cfg_tables.py holds every table and predicate of this module to the library's):
+# cfg -> (waves per workgroup, k chunk, non-temporal weight DMA, LDS ring slots, also a
+# cfg of the grouped MoE form). More than 3 slots (8-10): deep rings for M <= 16 -- more
+# weight bytes in flight per CU, one x tile only.
+# M64G_CFGS: cfg -> (waves, k chunk, nt), the three columns most callers unpack.
+M64G_TABLE = {0: (4, 128, False, 3, True), 1: (4, 128, True, 3, True), 2: (4, 64, False, 3, True),
+              3: (4, 64, True, 3, True), 4: (2, 64, False, 3, True), 5: (2, 64, True, 3, True),
+              6: (2, 128, True, 3, True), 7: (8, 64, True, 3, False),
+              8: (2, 128, True, 5, False), 9: (4, 128, True, 4, False), 10: (2, 64, True, 6, False)}
+M64G_CFGS = {cfg: row[:3] for cfg, row in M64G_TABLE.items()}
 # (Deep four-x-tile rings -- KC 64, 4-6 slots at M = 64 -- ran the 8B gate_up at 38.1
 # vs 41.7 us in isolation but +0.1 % end to end (10,756 vs 10,742 tok/s, 400 steps,
 # profiles/r6/r6s_m64g_sweep.md), and were not kept.)
-M64G_SMALL_ONLY = (8, 9, 10)
+M64_MAX_M = 64
+M64G_SMALL_ONLY = tuple(cfg for cfg, row in M64G_TABLE.items() if row[3] != 3)
 
 # Measured on MI355X with cold weights (bench/gemm_bench.py --m64g-sweep,
 # profiles/r1_m64g_sweep.jsonl; bucket 16 re-swept with the MT=1 kernel: r1_m64g_mt1_sweep.jsonl): (N, K, mode) -> {M bucket: (nw, split_k, cfg)}.
@@ -159,13 +165,15 @@ _M64_TUNED = {
 }
 
 
-def _apply_plan_overrides(spec: str) -> None:
-    """XGS_TUNE m64_plans="NxKxMODE@BUCKET=nw,S,cfg;..." replaces tuned plans (A/B sweeps)."""
+def _apply_plan_overrides(spec: str, tuned: Optional[dict] = None) -> None:
+    """XGS_TUNE m64_plans="NxKxMODE@BUCKET=nw,S,cfg;..." / mw_plans="NxKxMODE@BUCKET=S,cfg;..."
+    replace tuned plans of _M64_TUNED (the default) / _MW_TUNED (A/B sweeps)."""
+    tuned = _M64_TUNED if tuned is None else tuned
     for item in filter(None, (t.strip() for t in spec.split(";"))):
         key, plan = item.split("=")
         shape, bucket = key.split("@")
         n, k, mode = (int(v) for v in shape.split("x"))
-        _M64_TUNED.setdefault((n, k, mode), {})[int(bucket)] = tuple(int(v) for v in plan.split(","))
+        tuned.setdefault((n, k, mode), {})[int(bucket)] = tuple(int(v) for v in plan.split(","))
 
 
 _apply_plan_overrides(tune.get_str("m64_plans", ""))
@@ -174,7 +182,7 @@ _apply_plan_overrides(tune.get_str("m64_plans", ""))
 def _m64_valid(N: int, K: int, mode: int, nw: int, S: int, cfg: int, M: int = 1) -> bool:
     if cfg in M64G_SMALL_ONLY and M > 16:
         return False
-    wv, kc, _ = M64G_CFGS[cfg]
+    wv, kc = M64G_CFGS[cfg][:2]
     if N % (16 * nw * wv) or K % kc or S > K // kc:  # uneven split-K ranges are fine
         return False
     # split-K SiLU reduces its slabs in the GEMM's tail (m64g_silu_tail): NW = 2 pairs only
@@ -186,7 +194,7 @@ def m64_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL):
     from _M64_TUNED; otherwise split-K 4 whenever K allows (the partials are reduced
     by the consumer kernel for free), 128-column tiles once they give >= 192
     workgroups, else 64; bf16 / SiLU epilogues need split 1 (SiLU: nt weight DMA)."""
-    if not (1 <= M <= 64) or K % 256:
+    if not (1 <= M <= M64_MAX_M) or K % 256:
         return None
     t = _M64_TUNED.get((N, K, mode))
     if M <= 16:
@@ -219,8 +227,8 @@ def m64_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, split
     M, K = x.shape
     N = w.shape[0]
     plan = m64_plan(M, N, K, mode)
-    if plan is None and None not in (nw, split_k, cfg) and 1 <= M <= 64 and _m64_valid(N, K, mode, nw, split_k,
-                                                                                     cfg, M):
+    if (plan is None and None not in (nw, split_k, cfg) and 1 <= M <= M64_MAX_M
+            and _m64_valid(N, K, mode, nw, split_k, cfg, M)):
         plan = (nw, split_k, cfg)  # a fully explicit configuration (sweeps, tests) needs no measured plan
     if plan is None:
         raise ValueError(f"gemm_m64: unsupported shape M={M} N={N} K={K} mode={mode}")
@@ -252,13 +260,23 @@ def m64_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, split
 # csrc/kernels/gemm_mw.hip: one 8-wave workgroup per CU owns a 128- or 256-column
 # weight tile and every x row (x bytes per weight byte = M / columns), W and x both
 # by LDS-DMA, split-K partials for grids that would not fill the chip.
-# cfg -> (columns per workgroup, weight ring depth, non-temporal weight DMA)
+# cfg -> (columns per workgroup, weight ring depth, non-temporal weight DMA), the columns of
+# csrc/kernels/gemm_mw.hip MW_CFGS that a plan depends on
 # (0-4: 4 x 2 waves as N x M; 5-6: 2 x 4 waves -- fewer LDS fragment reads per MFMA.
 # The split-role and software-pipelined families of round 4 (cfg 7-21) never won a
 # default plan and were removed in round 5; their sweeps stay in profiles/r4_mw*.)
 MW_CFGS = {0: (256, 2, True), 1: (128, 3, True), 2: (128, 2, True), 3: (256, 2, False), 4: (128, 3, False),
            5: (128, 3, True), 6: (256, 2, True)}
 MW_MAX_M = 320   # M > 256 (a 320-row x tile) fits the LDS on cfg 2 only
+
+
+def _mw_fits(M: int, cfg: int) -> bool:
+    """The cfg's rings (depth + 1 weight slots, depth x slots of M rounded up to 64 rows;
+    128 B per row) fit the 160 KB LDS."""
+    cols, depth = MW_CFGS[cfg][:2]
+    return 1 <= M <= MW_MAX_M and ((depth + 1) * cols + depth * 64 * -(-M // 64)) * 128 <= 160 * 1024
+
+
 # (N, K, mode) -> {M bucket (128 / 192 / 256 / 320): (split_k, cfg)}, measured on MI355X with cold
 # weights (bench/gemm_bench.py --mw-sweep); other shapes take the default rule in mw_plan
 _MW_TUNED = {
@@ -300,7 +318,7 @@ def mw_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, plan=N
     M, K = x.shape
     N = w.shape[0]
     p = plan or mw_plan(M, N, K, mode)
-    if p is None or not x.is_contiguous():
+    if p is None or not x.is_contiguous() or not _mw_fits(M, p[1]):
         raise ValueError(f"gemm_mw: unsupported M={M} N={N} K={K} mode={mode}")
     S, cfg = p
     res, part, outp = _result(x, M, N, S, mode, out)
@@ -313,15 +331,17 @@ def mw_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, plan=N
 # in phases with the next tiles' LDS-DMA in flight across the barriers, waves 4-7 one
 # barrier behind waves 0-3 (MFMA / load ping-pong per SIMD). (A stream-K form measured
 # 164 vs 121 us at the 575-row gate_up and was removed, profiles/r5_pf_gemm.md.)
-# cfg -> (BM, m tiles per wave per phase): 0 (256, 2) 1 (192, 2) 2 (128, 2) 3 (256, 4)
-# 4 (192, 3) 5 (288, 3).
-PF_CFG_BM = {0: 256, 1: 192, 2: 128, 3: 256, 4: 192, 5: 288, 6: 288, 7: 256, 8: 192}
+# cfg -> (BM, m tiles per wave per phase, DMA lag in phases, also a cfg of the grouped MoE
+# form), the mirror of csrc/kernels/gemm_pf.hip PF_CFGS; PF_CFG_BM: cfg -> BM
+PF_CFGS = {0: (256, 2, 1, False), 1: (192, 2, 1, False), 2: (128, 2, 1, False), 3: (256, 4, 1, False),
+           4: (192, 3, 1, False), 5: (288, 3, 1, False), 6: (288, 3, 2, True), 7: (256, 2, 2, True),
+           8: (192, 2, 2, True)}
+PF_CFG_BM = {cfg: row[0] for cfg, row in PF_CFGS.items()}
 # The planner's cost model, fitted to bench/pf_gemm_bench.py at the 8B mixed-step
 # shapes (profiles/r5_pf_gemm.md): a workgroup costs PF_WG_US + its output bytes at
 # PF_WG_OUT_GBS (fp32 partials or bf16) + K tiles x the per-K-tile time of its cfg;
 # one workgroup per CU, so a grid of G costs ceil(G / CUs) of those.
 _PF_CFG_KT_US = {2: 1.07, 4: 1.34, 8: 1.37, 3: 1.75, 7: 1.51, 6: 1.77}   # cfg -> us per 64-deep K tile
-_PF_CFG_BM_ = {2: 128, 4: 192, 8: 192, 3: 256, 7: 256, 6: 288}
 PF_WG_US = 5.0
 PF_WG_OUT_GBS = 60.0
 
@@ -353,7 +373,7 @@ def pf_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
     nk = K // 64
     best = None
     for cfg, kt in _PF_CFG_KT_US.items():
-        bm = _PF_CFG_BM_[cfg]
+        bm = PF_CFG_BM[cfg]
         tiles = -(-M // bm) * (N // 256)
         ob = bm * 256 * (4 if mode == MODE_PARTIAL else 2)      # output bytes per workgroup
         wg = PF_WG_US + ob / (PF_WG_OUT_GBS * 1e3)
@@ -399,16 +419,7 @@ def lm_head_linear(h: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.linear(h, w)
 
 
-def _apply_mw_overrides(spec: str) -> None:
-    """XGS_TUNE mw_plans="NxKxMODE@BUCKET=S,cfg;..." replaces gemm_mw plans (A/B sweeps)."""
-    for item in filter(None, (t.strip() for t in spec.split(";"))):
-        key, plan = item.split("=")
-        shape, bucket = key.split("@")
-        n, k, mode = (int(v) for v in shape.split("x"))
-        _MW_TUNED.setdefault((n, k, mode), {})[int(bucket)] = tuple(int(v) for v in plan.split(","))
-
-
-_apply_mw_overrides(tune.get_str("mw_plans", ""))
+_apply_plan_overrides(tune.get_str("mw_plans", ""), _MW_TUNED)
 
 
 # ---------------------------------------------------------------------------- fused decode layer
@@ -594,8 +605,10 @@ def deinterleave_gate_up(w: torch.Tensor):
 # Weight-only FP8 (OCP E4M3 + one fp32 scale per output channel) for batch <= 16
 # decode: csrc/kernels/gemm_w8.hip streams half the bytes of the bf16 kernels.
 W8_MAX_M = 64
-# cfg -> (columns per workgroup, k chunk)
-W8_CFGS = {0: (128, 128), 1: (64, 128), 2: (64, 128), 3: (64, 256), 4: (128, 256)}
+# cfg -> (16-column tiles per wave, waves per workgroup, k chunk), the mirror of
+# csrc/kernels/gemm_w8.hip W8_CFGS; W8_CFGS: cfg -> (columns per workgroup, k chunk)
+W8_GEOM = {0: (2, 4, 128), 1: (2, 2, 128), 2: (1, 4, 128), 3: (2, 2, 256), 4: (2, 4, 256)}
+W8_CFGS = {cfg: (16 * nw * wv, kc) for cfg, (nw, wv, kc) in W8_GEOM.items()}
 # (N, K, mode) -> (split_k, cfg), measured at M = 1 / 16 with cold weights
 # (bench/gemm_bench.py --w8-sweep, profiles/r1_w8_sweep.jsonl)
 _W8_TUNED = {
@@ -730,8 +743,9 @@ def dequantize_into(q: torch.Tensor, scale: torch.Tensor, fmt: int, out: Optiona
 
 
 def _w8_fits(N: int, K: int, mode: int, S: int, cfg: int, M: int, fmt: int) -> bool:
-    cols, kc = W8_CFGS[cfg]
-    if N % cols or K % (S * kc) or (M > 16 and cfg >= 3) or (mode == MODE_SILU and (S != 1 or cfg == 2)):
+    (cols, kc), nw = W8_CFGS[cfg], W8_GEOM[cfg][0]
+    # 16 < M <= 64 (four x tiles): the KC 128 configurations; SiLU: a gate and an up tile per wave
+    if N % cols or K % (S * kc) or (M > 16 and kc != 128) or (mode == MODE_SILU and (S != 1 or nw != 2)):
         return False
     return fmt != WQ_INT4 or ((K // S) % WQ_GROUP == 0 and (K // S // WQ_GROUP) * cols <= WQ_SC_FLOATS)
 

@@ -23,8 +23,6 @@ MOE_CFG_W2 = 1
 # removed.
 MOE_PREFILL_PAIRS = 256
 MOE_CFG_W2_PREFILL = 3
-# waves per workgroup of each gemm_m64g cfg
-M64G_CFG_WAVES = {cfg: waves for cfg, (waves, _kc, _nt) in M64G_CFGS.items()}
 MOE_CFG_W13_PREFILL = 3
 # prefill-sized steps on gemm_pf's grouped form instead (csrc/kernels/gemm_pf.hip
 # gemm_pf_grouped): one MFMA tile of 192-288 rows covers an expert's rows, so each
@@ -52,6 +50,33 @@ def _moe_pf_cfg(pairs: int, E: int) -> int:
     expert's 64-padded segment."""
     seg = -(-max(1, pairs // max(1, E)) // BLOCK_M) * BLOCK_M
     return 8 if seg <= 192 else 7 if seg <= 256 else 6
+
+
+def moe_m64_plan(pairs: int, E: int, H: int, F: int):
+    """gemm_m64g configurations of a step's expert GEMMs (pairs = token-expert pairs, E local
+    experts): (cfg of w13 [2F, H], nw of w2 [H, F], cfg of w2, K splits of w2)."""
+    cfg13 = ((MOE_CFG_W13_PREFILL if pairs > MOE_PREFILL_PAIRS else
+              MOE_CFG_W13_BIG if MOE_W2_SMALL and pairs >= MOE_W13_BIG_PAIRS else MOE_CFG_W13)
+             if (H % 64 == 0 and (2 * F) % 128 == 0) else 0)
+    # w2 has only H/128 column tiles per expert: split K while few experts are active
+    nw2 = 2 if H % 128 == 0 else 1
+    cfg2 = (MOE_CFG_W2_PREFILL if pairs > MOE_PREFILL_PAIRS else MOE_CFG_W2) if nw2 == 2 else 0
+    kc2 = 128
+    S = 1
+    small = (MOE_W2_SMALL and (pairs <= MOE_W2_SMALL_LOW or MOE_W2_SMALL_HIGH <= pairs <= MOE_PREFILL_PAIRS)
+             and H % 64 == 0 and H // 64 <= 64)
+    if small:
+        nw2, cfg2 = 1, MOE_CFG_W2
+    for sk in (((2,) if pairs <= 8 else ()) if small else (4, 2) if pairs <= 4 else (2,) if pairs <= 16 else ()):
+        if F % (sk * kc2) == 0 and F % (sk * 256) == 0:
+            S = sk
+            break
+    cols2 = 16 * nw2 * M64G_CFGS[cfg2][0]
+    if S == 1 and (H // cols2) * E < 192 and F % (2 * kc2) == 0 and F % 512 == 0:
+        # few column tiles x local experts (EP shards: 4 experts x 32 tiles = 128
+        # workgroups on 256 CUs): 2 K splits fill the chip
+        S = 2
+    return cfg13, nw2, cfg2, S
 
 
 def _moe_pf_ok(H: int, F: int) -> bool:
@@ -219,29 +244,10 @@ def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torc
     # stops there instead of at the capacity P / 64
     def gemm(*a, cfg=0):
         kn.moe_gemm_m64g_rows(*a[:-1], cfg, max_rows, a[-1], valid, T * k)
-    cfg13 = ((MOE_CFG_W13_PREFILL if T * k > MOE_PREFILL_PAIRS else
-              MOE_CFG_W13_BIG if MOE_W2_SMALL and T * k >= MOE_W13_BIG_PAIRS else MOE_CFG_W13)
-             if (H % 64 == 0 and F2 % 128 == 0) else 0)
+    cfg13, nw2, cfg2, S = moe_m64_plan(T * k, E, H, F)
     gemm(x.contiguous().data_ptr(), sorted_rows.data_ptr(), offs.data_ptr(), E, H, w13.data_ptr(), F2, P, 0,
          act.data_ptr(), 1, 2, 2, stream_ptr(), cfg=cfg13)
-    # w2 has only H/128 column tiles per expert: split K while few experts are active
-    nw2 = 2 if H % 128 == 0 else 1
-    cfg2 = (MOE_CFG_W2_PREFILL if T * k > MOE_PREFILL_PAIRS else MOE_CFG_W2) if nw2 == 2 else 0
-    kc2 = 128
-    S = 1
-    small = (MOE_W2_SMALL and (T * k <= MOE_W2_SMALL_LOW or MOE_W2_SMALL_HIGH <= T * k <= MOE_PREFILL_PAIRS)
-             and H % 64 == 0 and H // 64 <= 64)
-    if small:
-        nw2, cfg2 = 1, MOE_CFG_W2
-    for sk in (((2,) if T * k <= 8 else ()) if small else (4, 2) if T * k <= 4 else (2,) if T * k <= 16 else ()):
-        if F % (sk * kc2) == 0 and F % (sk * 256) == 0:
-            S = sk
-            break
-    cols2 = 16 * nw2 * M64G_CFG_WAVES[cfg2]
-    if S == 1 and (H // cols2) * E < 192 and F % (2 * kc2) == 0 and F % 512 == 0:
-        # few column tiles x local experts (EP shards: 4 experts x 32 tiles = 128
-        # workgroups on 256 CUs): 2 K splits fill the chip
-        S = 2
+    cols2 = 16 * nw2 * M64G_CFGS[cfg2][0]
     part = torch.empty(S, P, H, dtype=torch.float32, device=x.device)
     if (resid is not None and counters is not None and max_rows <= MOE_PREFILL_PAIRS and H // cols2 <= 64
             and H // cols2 <= counters.numel()
