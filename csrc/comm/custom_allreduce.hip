@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../kernels/cfg_dispatch.h"
 #include "../kernels/common.h"
 #include "ll.h"
 
@@ -447,15 +448,10 @@ int custom_allreduce_resid_ll(const float* part, int S, int T, uint16_t* resid, 
   CarPtrs p{};
   for (int r = 0; r < world; ++r) p.data[r] = reinterpret_cast<uint8_t*>(data_ptrs[r]);
   const dim3 g(T, H / 1024);
-#define XGK_CARLL(SPV)                                                                                           \
-  hipLaunchKernelGGL((car_ll_resid_kernel<SPV>), g, dim3(128), 0, st, part, S, T, resid, ss_part, H, region_bytes, \
-                     p, rank, world, gens, err, loop)
-  if (S == 1) XGK_CARLL(1);
-  else if (S == 2) XGK_CARLL(2);
-  else if (S == 4) XGK_CARLL(4);
-  else if (S == 8) XGK_CARLL(8);
-  else XGK_CARLL(0);
-#undef XGK_CARLL
+  sp_dispatch<1, 2, 4, 8>(S, [&](auto sp) {
+    hipLaunchKernelGGL((car_ll_resid_kernel<decltype(sp)::value>), g, dim3(128), 0, st, part, S, T, resid, ss_part, H,
+                       region_bytes, p, rank, world, gens, err, loop);
+  });
   return 0;
 }
 
@@ -486,15 +482,10 @@ int custom_allreduce_resid(const float* part, int S, int T, uint16_t* resid, flo
     p.sig[r] = reinterpret_cast<uint32_t*>(sig_ptrs[r]);
   }
   const dim3 g(T, H / 1024);
-#define XGK_CARR(SPV)                                                                                          \
-  hipLaunchKernelGGL((car_resid_kernel<SPV>), g, dim3(128), 0, st, part, S, T, resid, ss_part, H, slot_bytes, p, \
-                     rank, world, gens, err)
-  if (S == 1) XGK_CARR(1);
-  else if (S == 2) XGK_CARR(2);
-  else if (S == 4) XGK_CARR(4);
-  else if (S == 8) XGK_CARR(8);
-  else XGK_CARR(0);
-#undef XGK_CARR
+  sp_dispatch<1, 2, 4, 8>(S, [&](auto sp) {
+    hipLaunchKernelGGL((car_resid_kernel<decltype(sp)::value>), g, dim3(128), 0, st, part, S, T, resid, ss_part, H,
+                       slot_bytes, p, rank, world, gens, err);
+  });
   return 0;
 }
 

@@ -17,7 +17,9 @@
 //   ep_plan / ep_scatter : expert-parallel dispatch -- deterministic per-destination
 //                      slots (fixed-capacity or count-exact packed layout), local
 //                      expert ids for the owners, the row copy into the send buffer.
+#include "cfg_dispatch.h"
 #include "common.h"
+#include "partials.h"
 
 namespace xgk {
 
@@ -421,7 +423,8 @@ void moe_align(const int32_t* ids, int T, int k, int E, int expert_offset, int b
 
 // ---------------------------------------------------------------- combine
 // out[t] = sum_j w[t, j] * sum_s part[s][dest[t*k + j]]   (dest < 0: another rank's expert)
-// y is either bf16 [P, H] (S == 0) or fp32 split-K partials [S, P, H].
+// y is either bf16 [P, H] (S == 0: SP == -1) or fp32 split-K partials [S, P, H] (SP == S,
+// partials.h).
 template <int SP>
 __global__ void __launch_bounds__(256) combine_kernel(const void* __restrict__ y, int S, int P,
                                                       const int32_t* __restrict__ dest, const float* __restrict__ w,
@@ -434,22 +437,11 @@ __global__ void __launch_bounds__(256) combine_kernel(const void* __restrict__ y
       if (p < 0) continue;
       const float wt = w[t * k + j];
       float f[8];
-      if constexpr (SP == 0) {
+      if constexpr (SP < 0) {
         unpack8(ld16(static_cast<const uint16_t*>(y) + static_cast<int64_t>(p) * H + c * 8), f);
       } else {
-        float4 a[SP], b[SP];
-#pragma unroll
-        for (int s = 0; s < SP; ++s) {
-          const float* q = static_cast<const float*>(y) + (static_cast<int64_t>(s) * P + p) * H + c * 8;
-          a[s] = *reinterpret_cast<const float4*>(q);
-          b[s] = *reinterpret_cast<const float4*>(q + 4);
-        }
         for (int i = 0; i < 8; ++i) f[i] = 0.f;
-#pragma unroll
-        for (int s = 0; s < SP; ++s) {
-          f[0] += a[s].x; f[1] += a[s].y; f[2] += a[s].z; f[3] += a[s].w;
-          f[4] += b[s].x; f[5] += b[s].y; f[6] += b[s].z; f[7] += b[s].w;
-        }
+        add_partials<8, SP>(static_cast<const float*>(y), S, P, p, H, c * 8, f);
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] += wt * f[i];
@@ -484,14 +476,7 @@ __global__ void __launch_bounds__(256) combine_resid_kernel(const float* __restr
       if (p < 0) continue;
       const float wt = w[t * k + j];
       float f[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int s = 0; s < SP; ++s) {
-        const float* q = part + (static_cast<int64_t>(s) * P + p) * H + c * 8;
-        const float4 a = *reinterpret_cast<const float4*>(q);
-        const float4 b = *reinterpret_cast<const float4*>(q + 4);
-        f[0] += a.x; f[1] += a.y; f[2] += a.z; f[3] += a.w;
-        f[4] += b.x; f[5] += b.y; f[6] += b.z; f[7] += b.w;
-      }
+      add_partials<8, SP>(part, SP, P, p, H, c * 8, f);
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] += wt * f[i];
     }
@@ -527,12 +512,9 @@ int moe_combine_resid(const float* part, int S, int P, const int32_t* dest, cons
   if (T <= 0) return 0;
   if (H % 1024 || H > 8192) return 1;
   const dim3 g(T), b(256);
-  switch (S) {
-    case 1: hipLaunchKernelGGL(combine_resid_kernel<1>, g, b, 0, st, part, P, dest, w, resid, ss, T, k, H); return 0;
-    case 2: hipLaunchKernelGGL(combine_resid_kernel<2>, g, b, 0, st, part, P, dest, w, resid, ss, T, k, H); return 0;
-    case 4: hipLaunchKernelGGL(combine_resid_kernel<4>, g, b, 0, st, part, P, dest, w, resid, ss, T, k, H); return 0;
-    default: return 1;
-  }
+  return sp_dispatch_exact<1, 2, 4>(S, [&](auto sp) {  // no runtime-S form: any other S is refused
+    hipLaunchKernelGGL(combine_resid_kernel<decltype(sp)::value>, g, b, 0, st, part, P, dest, w, resid, ss, T, k, H);
+  }) ? 0 : 1;
 }
 
 int moe_combine(const void* y, int S, int P, const int32_t* dest, const float* w, void* out, int T, int k, int H,
@@ -540,13 +522,11 @@ int moe_combine(const void* y, int S, int P, const int32_t* dest, const float* w
   if (T <= 0) return 0;
   if (H % 8) return 1;
   const dim3 g(T), b(256);
-  switch (S) {
-    case 0: hipLaunchKernelGGL(combine_kernel<0>, g, b, 0, st, y, S, P, dest, w, out, k, H, out_f32); return 0;
-    case 1: hipLaunchKernelGGL(combine_kernel<1>, g, b, 0, st, y, S, P, dest, w, out, k, H, out_f32); return 0;
-    case 2: hipLaunchKernelGGL(combine_kernel<2>, g, b, 0, st, y, S, P, dest, w, out, k, H, out_f32); return 0;
-    case 4: hipLaunchKernelGGL(combine_kernel<4>, g, b, 0, st, y, S, P, dest, w, out, k, H, out_f32); return 0;
-    default: return 1;
-  }
+  auto launch = [&](auto sp) {
+    hipLaunchKernelGGL(combine_kernel<decltype(sp)::value>, g, b, 0, st, y, S, P, dest, w, out, k, H, out_f32);
+  };
+  if (S == 0) return launch(Int<-1>{}), 0;  // bf16 rows
+  return sp_dispatch_exact<1, 2, 4>(S, launch) ? 0 : 1;  // no runtime-S form: any other S is refused
 }
 
 // ---------------------------------------------------------------- expert-parallel dispatch

@@ -15,7 +15,9 @@
 // contiguous block_size*D run, which is what the attention kernels stream.
 // slot_mapping < 0 marks padding tokens (graph-padded decode batch) that must
 // not write the cache.
+#include "cfg_dispatch.h"
 #include "common.h"
+#include "partials.h"
 
 namespace xgk {
 
@@ -26,36 +28,15 @@ struct QkvSrc {
   int S, T, width;
 };
 
-// SP > 0: exactly SP partials (all loads issued before the adds -- a runtime
-// trip count would serialise them into S dependent L2 round trips);
-// SP == 0: runtime S; SP < 0: bf16 row source.
+// f[0..8) = columns col .. col + 7 of token t: the bf16 row (SP == -1) or the sum of
+// the S fp32 slabs (partials.h: SP > 0 static, SP == 0 runtime S).
 template <int SP>
 __device__ __forceinline__ void qkv_load8(const QkvSrc& src, int t, int col, float* f) {
   if constexpr (SP < 0) {
     unpack8(ld16(src.row_bf16 + static_cast<int64_t>(t) * src.row_stride + col), f);
-  } else if constexpr (SP == 0) {
-    for (int i = 0; i < 8; ++i) f[i] = 0.f;
-    for (int s = 0; s < src.S; ++s) {
-      const float* p = src.part + (static_cast<int64_t>(s) * src.T + t) * src.width + col;
-      const float4 a = *reinterpret_cast<const float4*>(p);
-      const float4 b = *reinterpret_cast<const float4*>(p + 4);
-      f[0] += a.x; f[1] += a.y; f[2] += a.z; f[3] += a.w;
-      f[4] += b.x; f[5] += b.y; f[6] += b.z; f[7] += b.w;
-    }
   } else {
-    float4 a[SP], b[SP];
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      const float* p = src.part + (static_cast<int64_t>(s) * src.T + t) * src.width + col;
-      a[s] = *reinterpret_cast<const float4*>(p);
-      b[s] = *reinterpret_cast<const float4*>(p + 4);
-    }
     for (int i = 0; i < 8; ++i) f[i] = 0.f;
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      f[0] += a[s].x; f[1] += a[s].y; f[2] += a[s].z; f[3] += a[s].w;
-      f[4] += b[s].x; f[5] += b[s].y; f[6] += b[s].z; f[7] += b[s].w;
-    }
+    add_partials<8, SP>(src.part, src.S, src.T, t, src.width, col, f);
   }
 }
 
@@ -145,15 +126,12 @@ template <int D>
 static void launch_rope_d(dim3 g, QkvSrc src, uint16_t* q_out, int64_t q_stride, const int32_t* positions,
                           const float* cos_sin, uint16_t* k_cache, uint16_t* v_cache, const int32_t* slot_mapping,
                           int Hq, int Hkv, int block_size, int apply_rope, hipStream_t st) {
-#define XGK_ROPE(SPV) launch_rope_t<D, SPV>(g, src, q_out, q_stride, positions, cos_sin, k_cache, v_cache, \
-                                           slot_mapping, Hq, Hkv, block_size, apply_rope, st)
-  if (src.part == nullptr) XGK_ROPE(-1);
-  else if (src.S == 1) XGK_ROPE(1);
-  else if (src.S == 2) XGK_ROPE(2);
-  else if (src.S == 4) XGK_ROPE(4);
-  else if (src.S == 8) XGK_ROPE(8);
-  else XGK_ROPE(0);
-#undef XGK_ROPE
+  auto launch = [&](auto sp) {
+    launch_rope_t<D, decltype(sp)::value>(g, src, q_out, q_stride, positions, cos_sin, k_cache, v_cache, slot_mapping,
+                                          Hq, Hkv, block_size, apply_rope, st);
+  };
+  if (src.part == nullptr) launch(Int<-1>{});
+  else sp_dispatch<1, 2, 4, 8>(src.S, launch);
 }
 
 static int launch_rope(QkvSrc src, uint16_t* q_out, int64_t q_stride, const int32_t* positions, const float* cos_sin,

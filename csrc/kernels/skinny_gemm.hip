@@ -20,7 +20,9 @@
 //   * epilogue modes: bf16, fp32 partials, or SiLU-gate: with the block-16
 //     interleaved gate|up layout a workgroup's two n-tiles are the gate and up
 //     rows of the same 16 features -> silu(g)*u is written as [M, N/2].
+#include "cfg_dispatch.h"
 #include "common.h"
+#include "partials.h"
 
 namespace xgk {
 
@@ -331,9 +333,13 @@ int skinny_gemm(const uint16_t* x, int M, int K, const uint16_t* w, int N, float
 // ---------------------------------------------------------------------------
 // Split-K consumers
 // ---------------------------------------------------------------------------
+// The kernels that take a PendingSum's S fp32 slabs. partials.h is the one definition
+// of how they are summed (slab order, fp32, one rounding at the end, by the consumer)
+// and of the SP template argument (> 0: that many slabs, loads before adds; 0: runtime
+// S); the other consumers are in rope_cache.hip, decode_attention.hip, moe.hip,
+// gemm_m64g.hip's tails and comm/custom_allreduce.hip.
+//
 // residual[t] += sum_s part[s, t]; out[t] = rmsnorm(residual[t]) * w
-// SP > 0: compile-time partial count (every load of a chunk issued before the
-// adds); SP == 0: runtime S.
 template <int VPT, int SP>
 __global__ void __launch_bounds__(256) add_partials_rmsnorm_kernel(const float* __restrict__ part, int S, int T,
                                                                    uint16_t* __restrict__ residual,
@@ -350,6 +356,8 @@ __global__ void __launch_bounds__(256) add_partials_rmsnorm_kernel(const float* 
     const int c = threadIdx.x + k * blockDim.x;
     if (c < nchunk) {
       unpack8(ld16(rr + c * 8), v[k]);
+      // (not add_partials: with it every instantiation compiled differently and VPT 1 timed
+      // 0.4-1.6 % slower, profiles/partials_reader.md)
       if constexpr (SP > 0) {
         float4 a[SP], b[SP];
 #pragma unroll
@@ -399,25 +407,14 @@ void add_partials_rmsnorm(const float* part, int S, int T, uint16_t* residual, c
   if (T <= 0) return;
   const int nchunk = H / 8;
   const int thr = nchunk >= 256 ? 256 : ((nchunk + 63) / 64) * 64;
-  int vpt = (nchunk + thr - 1) / thr;
-  vpt = vpt <= 1 ? 1 : vpt <= 2 ? 2 : vpt <= 4 ? 4 : 8;
+  const int vpt = (nchunk + thr - 1) / thr;  // chunks per thread: VPT = the next of 1, 2, 4, 8
   dim3 g(T), b(thr);
-#define XGK_APR(V, SPV) hipLaunchKernelGGL((add_partials_rmsnorm_kernel<V, SPV>), g, b, 0, st, part, S, T, residual, \
-                                           w, out, H, eps)
-#define XGK_APR_S(V)            \
-  if (S == 1) XGK_APR(V, 1);    \
-  else if (S == 2) XGK_APR(V, 2); \
-  else if (S == 4) XGK_APR(V, 4); \
-  else if (S == 8) XGK_APR(V, 8); \
-  else XGK_APR(V, 0);
-  switch (vpt) {
-    case 1: XGK_APR_S(1); break;
-    case 2: XGK_APR_S(2); break;
-    case 4: XGK_APR_S(4); break;
-    default: XGK_APR_S(8); break;
-  }
-#undef XGK_APR_S
-#undef XGK_APR
+  sp_dispatch<1, 2, 4, 8>(S, [&](auto sp) {
+    cfg_dispatch<4>(vpt <= 1 ? 0 : vpt <= 2 ? 1 : vpt <= 4 ? 2 : 3, [&](auto lv) {
+      hipLaunchKernelGGL((add_partials_rmsnorm_kernel<1 << decltype(lv)::value, decltype(sp)::value>), g, b, 0, st,
+                         part, S, T, residual, w, out, H, eps);
+    });
+  });
 }
 
 // Fused decode layer, large split-K slabs (M ~ 64 decode): residual[t] +=
@@ -446,28 +443,7 @@ __global__ void __launch_bounds__(128) add_partials_resid_kernel(const float* __
   uint16_t* rr = residual + static_cast<int64_t>(t) * H + col;
   float v[8];
   unpack8(ld16(rr), v);
-  if constexpr (SP > 0) {
-    float4 a[SP], b[SP];
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      const float* pp = part + (static_cast<int64_t>(s) * T + t) * H + col;
-      a[s] = *reinterpret_cast<const float4*>(pp);
-      b[s] = *reinterpret_cast<const float4*>(pp + 4);
-    }
-#pragma unroll
-    for (int s = 0; s < SP; ++s) {
-      v[0] += a[s].x; v[1] += a[s].y; v[2] += a[s].z; v[3] += a[s].w;
-      v[4] += b[s].x; v[5] += b[s].y; v[6] += b[s].z; v[7] += b[s].w;
-    }
-  } else {
-    for (int s = 0; s < S; ++s) {
-      const float* pp = part + (static_cast<int64_t>(s) * T + t) * H + col;
-      const float4 a = *reinterpret_cast<const float4*>(pp);
-      const float4 b = *reinterpret_cast<const float4*>(pp + 4);
-      v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-      v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
-    }
-  }
+  add_partials<8, SP>(part, S, T, t, H, col, v);
   const uint4 pk = pack8(v);
   st16(rr, pk);
   unpack8(pk, v);  // statistics of the rounded (stored) residual
@@ -482,17 +458,14 @@ void add_partials_resid(const float* part, int S, int T, uint16_t* residual, flo
                         hipStream_t st, uint64_t sim_ticks) {
   if (T <= 0) return;
   const dim3 g(T * (H / 1024));
-#define XGK_APRS(SPV) \
-  hipLaunchKernelGGL((add_partials_resid_kernel<SPV>), g, dim3(128), 0, st, part, S, T, residual, ss_part, H, sim_ticks)
-  if (S == 1) XGK_APRS(1);
-  else if (S == 2) XGK_APRS(2);
-  else if (S == 4) XGK_APRS(4);
-  else if (S == 8) XGK_APRS(8);
-  else XGK_APRS(0);
-#undef XGK_APRS
+  sp_dispatch<1, 2, 4, 8>(S, [&](auto sp) {
+    hipLaunchKernelGGL((add_partials_resid_kernel<decltype(sp)::value>), g, dim3(128), 0, st, part, S, T, residual,
+                       ss_part, H, sim_ticks);
+  });
 }
 
-// out[t, :] = bf16(sum_s part[s, t, :])  (used when a collective needs the sum)
+// out[t, :] = bf16(sum_s part[s, t, :])  (used when a collective needs the sum). A flat
+// 64-bit index over [S][n], so not add_partials' (row, col) ints; the same slab order.
 __global__ void __launch_bounds__(256) reduce_partials_kernel(const float* __restrict__ part, int S, int64_t n,
                                                               uint16_t* __restrict__ out) {
   for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n / 4;

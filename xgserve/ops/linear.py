@@ -26,6 +26,9 @@ _SPLITS = (1, 2, 4, 7, 8, 14, 16)
 
 @dataclass
 class PendingSum:
+    """S fp32 split-K slabs of a value nobody has summed yet. The consuming kernel adds them
+    in slab order, in fp32, and rounds once at its own end: csrc/kernels/partials.h is the one
+    definition of that order (and of the kernels' SP template argument)."""
     part: torch.Tensor  # [S, M, N] fp32
     S: int
 
