@@ -48,6 +48,13 @@ void sample_tokens(const void*, int, int64_t, int, int, const float*, const floa
 size_t sample_ws_row_bytes();
 void segment_sum(const uint16_t*, int, const int32_t*, const int32_t*, float*, int, hipStream_t);
 void subst_tokens(int32_t*, const int32_t*, const int32_t*, int, hipStream_t);
+int process_logits(const void*, int, int64_t, float*, int64_t, int, int, const uint16_t*, int, const int32_t*,
+                   const float*, int, const float*, const int32_t*, const float*, int, float*, hipStream_t);
+int logit_state_reset(uint16_t*, int, int, const int32_t*, int, const int32_t*, const int32_t*, int, hipStream_t);
+int logit_state_update(uint16_t*, int, int, const int32_t*, const int32_t*, int, hipStream_t);
+int logit_proc_parts(int);
+int logit_bias_max();
+int logit_count_max();
 int dequant_w8(const uint8_t*, const float*, int, int, uint16_t*, int, hipStream_t);
 void moe_topk_softmax(const void*, int, int, int, int, int, float*, int32_t*, hipStream_t);
 void moe_align(const int32_t*, int, int, int, int, int, int32_t*, int32_t*, int32_t*, hipStream_t);
@@ -217,6 +224,34 @@ PYBIND11_MODULE(_kernels, m) {
     xgk::subst_tokens(P<int32_t>(ids), P<const int32_t>(src), P<const int32_t>(prev), n, S(st));
     check(0, "subst_tokens");
   });
+  // logit processors (logit_proc.hip). pi: [slot | bias offset | bias length] x pstride int32,
+  // pf: [repetition | frequency | presence | ln(min_p)] x pstride floats, ws: rows x
+  // logit_proc_parts(V) floats; state: num_slots x V uint16 cells (0: no tracked row)
+  m.def("process_logits", [](uintptr_t in, int is_f32, int64_t in_stride, uintptr_t out, int64_t out_stride, int rows,
+                             int V, uintptr_t state, int num_slots, uintptr_t pi, uintptr_t pf, int pstride,
+                             uintptr_t temps, uintptr_t bias_ids, uintptr_t bias_vals, int bias_cap, uintptr_t ws,
+                             uintptr_t st) {
+    check(xgk::process_logits(P<const void>(in), is_f32, in_stride, P<float>(out), out_stride, rows, V,
+                              P<const uint16_t>(state), num_slots, P<const int32_t>(pi), P<const float>(pf), pstride,
+                              P<const float>(temps), P<const int32_t>(bias_ids), P<const float>(bias_vals), bias_cap,
+                              P<float>(ws), S(st)),
+          "process_logits");
+  });
+  m.def("logit_state_reset", [](uintptr_t state, int num_slots, int V, uintptr_t desc, int nres, uintptr_t ids,
+                                uintptr_t cells, int total, uintptr_t st) {
+    check(xgk::logit_state_reset(P<uint16_t>(state), num_slots, V, P<const int32_t>(desc), nres,
+                                 P<const int32_t>(ids), P<const int32_t>(cells), total, S(st)),
+          "logit_state_reset");
+  });
+  m.def("logit_state_update", [](uintptr_t state, int num_slots, int V, uintptr_t slots, uintptr_t toks, int n,
+                                 uintptr_t st) {
+    check(xgk::logit_state_update(P<uint16_t>(state), num_slots, V, P<const int32_t>(slots), P<const int32_t>(toks),
+                                  n, S(st)),
+          "logit_state_update");
+  });
+  m.def("logit_proc_parts", &xgk::logit_proc_parts);
+  m.def("logit_bias_max", &xgk::logit_bias_max);
+  m.def("logit_count_max", &xgk::logit_count_max);
   m.def("segment_sum", [](uintptr_t hidden, int H, uintptr_t cu, uintptr_t rows, uintptr_t out, int nseg,
                           uintptr_t st) {
     if (H % 8) throw std::invalid_argument("segment_sum: H % 8 != 0");

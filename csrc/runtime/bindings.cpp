@@ -170,6 +170,11 @@ PYBIND11_MODULE(_runtime, m) {
            [](const RequestValidator& v, const std::vector<std::string>& in) {
              return vres(v.validate_embeddings(in));
            })
+      .def("check_processors",
+           [](const RequestValidator& v, float min_p, float rp, float pp, float fp,
+              const std::vector<uint64_t>& ids, const std::vector<float>& vals, uint64_t vocab) {
+             return vres(v.check_processors(min_p, rp, pp, fp, ids, vals, vocab));
+           })
       .def("config", &RequestValidator::config)
       .def("set_config", &RequestValidator::set_config);
 

@@ -111,6 +111,44 @@ ValidationResult RequestValidator::check_sampling(size_t max_tokens, float tempe
   return ValidationResult{};
 }
 
+static bool outside(float v, float lo, float hi) { return std::isnan(v) || v < lo || v > hi; }
+
+ValidationResult RequestValidator::check_processors(float min_p, float repetition_penalty,
+                                                    float presence_penalty, float frequency_penalty,
+                                                    const std::vector<uint64_t>& bias_ids,
+                                                    const std::vector<float>& bias_values,
+                                                    uint64_t vocab_size) const {
+  if (outside(min_p, 0.0f, 1.0f))
+    return invalid_param("min_p", "must be between 0 and 1, got " + rust_f32_display(min_p));
+  if (outside(repetition_penalty, 0.0f, 2.0f) || repetition_penalty == 0.0f)
+    return invalid_param("repetition_penalty", "must be greater than 0 and at most 2, got " +
+                                                   rust_f32_display(repetition_penalty));
+  if (outside(presence_penalty, -2.0f, 2.0f))
+    return invalid_param("presence_penalty",
+                         "must be between -2 and 2, got " + rust_f32_display(presence_penalty));
+  if (outside(frequency_penalty, -2.0f, 2.0f))
+    return invalid_param("frequency_penalty",
+                         "must be between -2 and 2, got " + rust_f32_display(frequency_penalty));
+  if (bias_ids.size() != bias_values.size())
+    return invalid_param("logit_bias", "token ids and values differ in number");
+  if (bias_ids.size() > kMaxLogitBias)
+    return invalid_param("logit_bias", "must have at most " + std::to_string(kMaxLogitBias) +
+                                           " entries, got " + std::to_string(bias_ids.size()));
+  for (size_t i = 0; i < bias_ids.size(); ++i) {
+    if (vocab_size != 0 && bias_ids[i] >= vocab_size)
+      return invalid_param("logit_bias", "token id " + std::to_string(bias_ids[i]) +
+                                             " is outside the vocabulary of " + std::to_string(vocab_size));
+    for (size_t j = 0; j < i; ++j)
+      if (bias_ids[j] == bias_ids[i])
+        return invalid_param("logit_bias", "token id " + std::to_string(bias_ids[i]) + " is given twice");
+    if (outside(bias_values[i], -100.0f, 100.0f))
+      return invalid_param("logit_bias", "bias of token " + std::to_string(bias_ids[i]) +
+                                             " must be between -100 and 100, got " +
+                                             rust_f32_display(bias_values[i]));
+  }
+  return ValidationResult{};
+}
+
 ValidationResult RequestValidator::validate_generate(const std::string& prompt, size_t max_tokens,
                                                      float temperature, float top_p) const {
   if (is_blank_utf8(prompt)) return empty_prompt();

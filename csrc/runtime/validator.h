@@ -73,6 +73,15 @@ class RequestValidator {
   ValidationResult validate_chat(const std::vector<std::string>& contents,
                                  size_t max_tokens, float temperature, float top_p) const;
   ValidationResult validate_embeddings(const std::vector<std::string>& inputs) const;
+  // Extension fields (not in the reference's serde models): min_p in [0, 1],
+  // repetition_penalty in (0, 2], presence / frequency penalty in [-2, 2], at most
+  // kMaxLogitBias logit_bias entries with distinct ids < vocab_size (0: unknown, not
+  // checked) and values in [-100, 100]; NaN is rejected everywhere. First failing
+  // check wins, in that order.
+  static constexpr size_t kMaxLogitBias = 128;
+  ValidationResult check_processors(float min_p, float repetition_penalty, float presence_penalty,
+                                    float frequency_penalty, const std::vector<uint64_t>& bias_ids,
+                                    const std::vector<float>& bias_values, uint64_t vocab_size) const;
 
   const ValidatorConfig& config() const { return cfg_; }
   void set_config(const ValidatorConfig& c) { cfg_ = c; }

@@ -161,6 +161,41 @@ def _sampling(d: dict) -> dict:
     }
 
 
+MAX_LOGIT_BIAS = 128
+
+
+def _logit_bias(v: Any) -> Dict[int, float]:
+    """`logit_bias`: an object mapping a decimal token-id string to a number."""
+    if not isinstance(v, dict):
+        raise ValidationError.invalid_json("invalid type for `logit_bias`: expected a map of token id to f32")
+    out: Dict[int, float] = {}
+    for k, b in v.items():
+        if not (isinstance(k, str) and k.isascii() and k.isdigit()) or int(k) > 2**64 - 1:
+            raise ValidationError.invalid_json(f"invalid key `{k}` in `logit_bias`: expected a decimal token id")
+        t = int(k)
+        if t in out:  # "7" and "007"
+            raise ValidationError.invalid_parameter("logit_bias", f"token id {t} is given twice")
+        out[t] = _f32_field(b, f"logit_bias[{k}]")
+    return out
+
+
+def _processors(d: dict) -> dict:
+    """Sampling extensions (not in the reference's serde models, like `seed`): strict
+    types here, ranges in the validator (RequestValidator.check_processors)."""
+    out = {}
+    if d.get("top_k") is not None:
+        out["top_k"] = _usize(d["top_k"], "top_k")
+    for name in ("min_p", "repetition_penalty", "presence_penalty", "frequency_penalty"):
+        if d.get(name) is not None:
+            out[name] = _f32_field(d[name], name)
+    if d.get("logit_bias") is not None:
+        out["logit_bias"] = _logit_bias(d["logit_bias"])
+    return out
+
+
+PROCESSOR_FIELDS = ("top_k", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias")
+
+
 # ---------------------------------------------------------------------------
 # Requests (models.rs:55-139)
 # ---------------------------------------------------------------------------
@@ -177,6 +212,12 @@ class GenerateRequest:
     seed: Optional[int] = None
     logprobs: bool = False
     ignore_eos: bool = False
+    top_k: int = 0
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Dict[int, float] = field(default_factory=dict)
 
     @classmethod
     def parse(cls, body: Union[bytes, str, dict]) -> "GenerateRequest":
@@ -193,7 +234,7 @@ class GenerateRequest:
                 raise ValidationError.invalid_json(str(e))
         return cls(prompt=prompt, priority=pr, seed=_opt_int(d, "seed"),
                    logprobs=bool(d.get("logprobs", False)) if isinstance(d.get("logprobs", False), bool) else False,
-                   ignore_eos=d.get("ignore_eos") is True, **s)
+                   ignore_eos=d.get("ignore_eos") is True, **s, **_processors(d))
 
 
 def _opt_int(d: dict, name: str) -> Optional[int]:
@@ -213,6 +254,12 @@ class ChatRequest:
     stream: bool = False
     seed: Optional[int] = None
     ignore_eos: bool = False
+    top_k: int = 0
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Dict[int, float] = field(default_factory=dict)
 
     @classmethod
     def parse(cls, body: Union[bytes, str, dict]) -> "ChatRequest":
@@ -223,7 +270,7 @@ class ChatRequest:
             raise ValidationError.invalid_json("invalid type for `messages`: expected a sequence")
         msgs = [ChatMessage.from_dict(m) for m in d["messages"]]
         return cls(messages=msgs, seed=_opt_int(d, "seed"), ignore_eos=d.get("ignore_eos") is True,
-                   **_sampling(d))
+                   **_sampling(d), **_processors(d))
 
 
 @dataclass

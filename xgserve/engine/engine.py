@@ -33,7 +33,7 @@ from ..models import build_model, get_config
 from ..parallel import comm
 from ..parallel.state import get_state
 from .request import (FINISH_ABORT, FINISH_EMBED, FINISH_LENGTH, FINISH_NAMES, FINISH_STOP, FINISH_STOP_SEQ,
-                      EngineRequest, RequestOutput, RequestType, SamplingParams)
+                      EngineRequest, RequestOutput, RequestType, SamplingParams, UnsupportedSampling)
 from .runner import ModelRunner, SamplingRows
 from .tokenizer import IncrementalDetokenizer, load_tokenizer
 
@@ -212,6 +212,15 @@ class LLMEngine:
         self.slot_topk = np.zeros(ns, np.int32)
         self.slot_seed = np.zeros(ns, np.uint64)
         self.slot_ngen = np.zeros(ns, np.int64)  # tokens generated by the slot's owner (sampling counter)
+        # logit processors: repetition | frequency | presence penalty | ln(min_p) per slot, the
+        # slot's row of the device state table (-1: the owner needs no token statistics),
+        # its number of logit_bias entries, and whether the owner is not plain
+        self.slot_pen = np.zeros((4, ns), np.float32)
+        self.slot_pen[0], self.slot_pen[3] = 1.0, -np.inf
+        self.slot_track = np.full(ns, -1, np.int32)
+        self.slot_blen = np.zeros(ns, np.int32)
+        self.slot_proc = np.zeros(ns, bool)
+        self._resets: Dict[int, tuple] = {}  # slot -> state reset awaiting the next processed step
         self._deferred = None  # (plan, toks, lps, counts, fin_map) awaiting detokenisation
         # callable(List[RequestOutput]) taking overlap-window outputs immediately (a server
         # replica sets it); None: every output is returned by step()
@@ -277,6 +286,8 @@ class LLMEngine:
         if min(prompt_ids) < 0 or max(prompt_ids) >= V:
             # an id outside the embedding table would be an out-of-bounds gather on the GPU
             raise ValueError(f"prompt token ids must be in [0, {V}), got [{min(prompt_ids)}, {max(prompt_ids)}]")
+        if not params.plain:
+            self._check_processors(params)
         max_tokens = params.max_tokens
         if kind != RequestType.Embeddings:
             max_tokens = min(max_tokens, self.max_model_len - len(prompt_ids))
@@ -301,6 +312,37 @@ class LLMEngine:
         if max_tokens <= 0 and kind != RequestType.Embeddings:
             self.abort(request_id, reason=FINISH_LENGTH)
         return req
+
+    def _check_processors(self, params: SamplingParams) -> None:
+        """What the device path relies on (the HTTP validator checks the documented
+        ranges; this guards direct callers too)."""
+        from ..ops import LOGIT_BIAS_MAX
+        if self.spec is not None:
+            # verification samples k + 1 positions of a row in one step, each with a
+            # different history: processed verification is not built
+            names = [n for n, neutral in (("min_p", 0.0), ("repetition_penalty", 1.0), ("presence_penalty", 0.0),
+                                          ("frequency_penalty", 0.0), ("logit_bias", {}))
+                     if getattr(params, n) != neutral]
+            raise UnsupportedSampling(names[0], "is not supported together with speculative decoding")
+        for n in ("min_p", "repetition_penalty", "presence_penalty", "frequency_penalty"):
+            if not math.isfinite(float(getattr(params, n))):
+                raise UnsupportedSampling(n, "must be a finite number")
+        if not 0.0 <= params.min_p <= 1.0:
+            raise UnsupportedSampling("min_p", f"must be between 0 and 1, got {params.min_p}")
+        if not params.repetition_penalty > 0.0:
+            raise UnsupportedSampling("repetition_penalty", f"must be greater than 0, got {params.repetition_penalty}")
+        bias = {int(t): float(b) for t, b in params.logit_bias.items()}
+        if len(bias) != len(params.logit_bias):
+            raise UnsupportedSampling("logit_bias", "a token id is given twice")
+        if len(bias) > LOGIT_BIAS_MAX:
+            raise UnsupportedSampling("logit_bias", f"must have at most {LOGIT_BIAS_MAX} entries, got {len(bias)}")
+        V = self.mcfg.vocab_size
+        for t, b in bias.items():
+            if not 0 <= t < V:
+                raise UnsupportedSampling("logit_bias", f"token id {t} is outside the vocabulary of {V}")
+            if not math.isfinite(b):
+                raise UnsupportedSampling("logit_bias", f"bias of token {t} must be a finite number")
+        params.logit_bias = bias
 
     def abort(self, request_id: str, reason: int = FINISH_ABORT) -> bool:
         with self._lock:
@@ -335,12 +377,51 @@ class LLMEngine:
             self.slot_owner[s] = sid
             self.slot_req[s] = r
             self.slot_ngen[s] = len(r.output_ids) if r is not None else 0
+            self.slot_pen[:, s] = (1.0, 0.0, 0.0, -np.inf)
+            self.slot_track[s], self.slot_blen[s], self.slot_proc[s] = -1, 0, False
+            self._resets.pop(s, None)
             if r is None:
                 self.slot_temp[s], self.slot_topp[s], self.slot_topk[s], self.slot_seed[s] = 0.0, 1.0, 0, 0
                 continue
             p = r.params
             self.slot_temp[s], self.slot_topp[s], self.slot_topk[s] = p.temperature, p.top_p, p.top_k
             self.slot_seed[s] = np.uint64(p.seed & _MASK63)
+            if not p.plain:
+                self._bind_processors(s, r)
+
+    def _bind_processors(self, s: int, r: EngineRequest) -> None:
+        """Slot s got an owner that is not plain: its per-slot parameters, and -- if it
+        needs token statistics -- the reset of the slot's state-table row from the
+        prompt and every token committed so far (a sequence resumed after pre-emption
+        is bound again and carries its history), enqueued ahead of its first step."""
+        from .. import ops
+        p = r.params
+        self.slot_proc[s] = True
+        self.slot_pen[:, s] = (p.repetition_penalty, p.frequency_penalty, p.presence_penalty,
+                               math.log(p.min_p) if p.min_p > 0.0 else -np.inf)
+        if not p.needs_counts:
+            return
+        self.slot_track[s] = s
+        self.slot_blen[s] = len(p.logit_bias)
+        ids, cells = ops.logit_state_cells(r.prompt_ids, self._committed_ids(r))
+        self._resets[s] = (s, ids, cells, np.fromiter(p.logit_bias.keys(), np.int32, len(p.logit_bias)),
+                           np.fromiter(p.logit_bias.values(), np.float32, len(p.logit_bias)))
+
+    def _committed_ids(self, r: EngineRequest) -> List[int]:
+        """Every token the scheduler holds for r: output_ids plus what a deferred
+        emission (overlap_outputs) has not appended yet."""
+        ids = list(r.output_ids)
+        d = self._deferred
+        if d is None or (len(d) == 6 and r.seq_id in d[5]):
+            return ids
+        plan, toks, _, counts = d[:4]
+        sidx, seq_ids, k = plan["sample_seq_index"], plan["seq_ids"], 0
+        for j in range(int(plan["num_sample"])):
+            c = int(counts[j])
+            if int(seq_ids[sidx[j]]) == r.seq_id:
+                ids.extend(int(t) for t in toks[k:k + c])
+            k += c
+        return ids
 
     def _sampling_rows(self, plan) -> Optional[SamplingRows]:
         if not self.is_driver:
@@ -362,7 +443,12 @@ class LLMEngine:
                 x ^= x >> np.uint64(29)
                 x = (x * np.uint64(0xBF58476D1CE4E5B9)) & np.uint64(_MASK63)
             seeds = x.view(np.int64)
-        return SamplingRows(temps, self.slot_topp[slots], self.slot_topk[slots], seeds)
+        samp = SamplingRows(temps, self.slot_topp[slots], self.slot_topk[slots], seeds)
+        if self.slot_proc[slots].any():
+            samp.slots, samp.bias_lens, samp.pens = self.slot_track[slots], self.slot_blen[slots], self.slot_pen[:, slots]
+            if self._resets:
+                samp.resets, self._resets = list(self._resets.values()), {}
+        return samp
 
     def _torch_profile_tick(self) -> None:
         """XGS_TORCH_PROFILE=N: record the next N steps with torch.profiler (CPU +
@@ -506,13 +592,20 @@ class LLMEngine:
             plan = self.sched.schedule()
         t = self._tick("schedule", t)
         st = get_state()
+        samp = None
+        if plan["num_tokens"] > 0:
+            if self.is_driver:
+                self._bind_slots(plan)
+            samp = self._sampling_rows(plan)
         if st.tp_size > 1:
-            comm.tp_broadcast_object(("plan", plan), src=0)
+            if samp is not None and samp.processed:
+                # the followers mirror a processed step whole (slot resets, the lazily
+                # captured graph and its warm-up forward with its collectives, sampling)
+                comm.tp_broadcast_object(("launch", (plan, samp, None)), src=0)
+            else:
+                comm.tp_broadcast_object(("plan", plan), src=0)
         if plan["num_tokens"] == 0:
             return outs + self._flush_deferred()
-        if self.is_driver:
-            self._bind_slots(plan)
-        samp = self._sampling_rows(plan)
         t = self._tick("prepare", t)
         counts = None
         if self.spec is not None and self.is_driver and plan["num_seqs"] > plan["num_decodes"]:

@@ -11,7 +11,7 @@ from __future__ import annotations
 import enum
 import time
 from dataclasses import dataclass, field
-from typing import Any, Callable, List, Optional
+from typing import Any, Callable, Dict, List, Optional
 
 
 class RequestType(str, enum.Enum):
@@ -32,6 +32,32 @@ class SamplingParams:
     min_tokens: int = 0
     seed: Optional[int] = None
     logprobs: bool = False
+    # logit processors (ops/sampling.py process_logits), all neutral by default
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Dict[int, float] = field(default_factory=dict)
+
+    @property
+    def needs_counts(self) -> bool:
+        """The sequence's token statistics (and its bias list) must live on the device."""
+        return bool(self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                    or self.frequency_penalty != 0.0 or self.logit_bias)
+
+    @property
+    def plain(self) -> bool:
+        """No logit processor applies: the samplers read the model's logits as they are."""
+        return not (self.needs_counts or self.min_p > 0.0)
+
+
+class UnsupportedSampling(ValueError):
+    """A request's sampling parameters cannot be served by this engine: `field` and
+    `reason` as in the validator's InvalidParameter (the server answers 400)."""
+
+    def __init__(self, field: str, reason: str):
+        super().__init__(f"{field}: {reason}")
+        self.field, self.reason = field, reason
 
 
 # finish reason codes shared with csrc/runtime/scheduler.h (SeqFinish)

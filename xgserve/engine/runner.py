@@ -19,6 +19,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import gc
 import logging
 import math
@@ -53,10 +54,22 @@ class SamplingRows:
     top_ps: np.ndarray
     top_ks: np.ndarray
     seeds: np.ndarray  # int64, already mixed with the step counter
+    # logit processors (ops.process_logits); None: every row is plain and the step
+    # enqueues exactly what it did before they existed
+    slots: Optional[np.ndarray] = None      # int32 state-table slot per row, -1: no history
+    bias_lens: Optional[np.ndarray] = None  # int32 logit_bias entries per row (at slot * LOGIT_BIAS_MAX)
+    pens: Optional[np.ndarray] = None       # float32 [4, rows]: repetition | frequency | presence | ln(min_p)
+    # slots bound since the last processed step, reset ahead of this one on every rank:
+    # [(slot, unique ids, cells, bias ids, bias values)]
+    resets: Optional[list] = None
 
     @property
     def all_greedy(self) -> bool:
         return bool((self.temps <= 0).all())
+
+    @property
+    def processed(self) -> bool:
+        return self.pens is not None
 
 
 def _pinned(n: int, dtype) -> torch.Tensor:
@@ -174,6 +187,15 @@ class ModelRunner:
                 self.mixed_chunk = 0
         self._graph_pool = None
         self._init_graph_buffers()
+        # logit processors: nothing of this exists until a request asks for one (_proc_init)
+        self.p_state = None           # [max_num_seqs, V] prompt flag | generated count per slot (_state_init)
+        self.p_bias_ids = self.p_bias_vals = None   # per-slot logit_bias lists, allocated with the table
+        self.p_scratch = None         # fp32 processed logits of a graph step
+        self.proc_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (bucket, greedy), captured at first need
+        self.proc_mixed_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
+        self._rst_pin = [None, None]  # reset staging: pinned buffers + events
+        self._rst_ev = [None, None]
+        self._rst_idx = 0
         # custom all-reduce peer-wait limit while serving (EngineConfig.collective_timeout_s);
         # warmup, graph capture and the first WARM_LAUNCHES steps run under the warmup limit
         self.collective_timeout_s = 2.0
@@ -250,13 +272,15 @@ class ModelRunner:
             self.h_mints = [_pinned(n_m, torch.int32) for _ in range(2)]
             self.h_mlidx = [_pinned(B + 1, torch.int64) for _ in range(2)]
 
-    def _decode_body(self, bs: int, greedy: bool):
+    def _decode_body(self, bs: int, greedy: bool, proc: bool = False):
         ops.subst_tokens(self.g_ids[:bs], self.g_src[:bs], self.g_out_tok)
         meta = AttnMeta(num_tokens=bs, num_decodes=bs, positions=self.g_pos[:bs], slot_mapping=self.g_slot[:bs],
                         dec_block_tables=self.g_bt[:bs], dec_seq_lens=self.g_sl[:bs],
                         num_splits=self.decode_splits(bs), workspace=self.workspace)
         h = self.model(self.g_ids[:bs], meta, self.kv_caches)
         logits = self.model.compute_logits(h)
+        if proc:
+            logits = self._process_graph_rows(logits, bs)
         if greedy:
             ops.argmax_logprob(logits, self.g_out_tok[:bs], self.g_out_lp[:bs])
         else:
@@ -264,8 +288,10 @@ class ModelRunner:
                                         self.g_seed[:bs], step=0)
             self.g_out_tok[:bs].copy_(tok)
             self.g_out_lp[:bs].copy_(lp)
+        if proc and self.p_state is not None:
+            ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, bs)
 
-    def _mixed_body(self, nb: int, greedy: bool):
+    def _mixed_body(self, nb: int, greedy: bool, proc: bool = False):
         """nb decode rows (padded) + one prompt chunk of up to C rows (padded) -> the
         sampled tokens of the decode rows and the chunk's last row (g_out_tok[:nb + 1])."""
         B, C = self.g_B, self.mixed_chunk
@@ -287,6 +313,8 @@ class ModelRunner:
                         pre_max_q=C)
         h = self.model(ids_t, meta, self.kv_caches)
         logits = self.model.compute_logits(h.index_select(0, self.m_lidx[:nb + 1]))
+        if proc:
+            logits = self._process_graph_rows(logits, nb + 1)
         if greedy:
             ops.argmax_logprob(logits, self.g_out_tok[:nb + 1], self.g_out_lp[:nb + 1])
         else:
@@ -294,6 +322,183 @@ class ModelRunner:
                                         self.g_seed[:nb + 1], step=0)
             self.g_out_tok[:nb + 1].copy_(tok)
             self.g_out_lp[:nb + 1].copy_(lp)
+        if proc and self.p_state is not None:
+            ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, nb + 1)
+
+    # ------------------------------------------------------------------ logit processors
+    def _proc_init(self) -> None:
+        """Per-row parameter buffers and the fp32 scratch of graph steps: allocated by the
+        first step that is not plain, out of the gpu_memory_utilization headroom (the KV
+        pool was sized before)."""
+        if hasattr(self, "g_pi"):
+            return
+        V = self.cfg.vocab_size
+        R = self.g_OB
+        # [slot | bias offset | bias length] and [repetition | frequency | presence | ln(min_p)] per row
+        self.g_pi = torch.zeros(3, R, dtype=torch.int32, device=self.device)
+        self.g_pi[0].fill_(-1)
+        self.g_pf = torch.zeros(4, R, dtype=torch.float32, device=self.device)
+        self.h_pis = [_pinned(3 * R, torch.int32) for _ in range(2)]
+        self.h_pfs = [_pinned(4 * R, torch.float32) for _ in range(2)]
+        if self.use_graphs:
+            self.p_scratch = ops.process_scratch(R, V, self.device)
+
+    def _state_init(self) -> None:
+        """The state table and the per-slot bias lists: allocated by the first request
+        that needs token statistics (min_p alone does not). Processed graphs captured
+        before hold no table; they are keyed apart from those captured after."""
+        if self.p_state is not None:
+            return
+        V, ns, nb = self.cfg.vocab_size, self.max_num_seqs, ops.LOGIT_BIAS_MAX
+        self.p_state = ops.logit_state_alloc(ns, V, self.device)
+        self.p_bias_ids = torch.zeros(ns * nb, dtype=torch.int32, device=self.device)
+        self.p_bias_vals = torch.zeros(ns * nb, dtype=torch.float32, device=self.device)
+        log.info("logit processors: state table %d x %d (%.1f MiB)", ns, V, ns * V * 2 / 2**20)
+
+    def _apply_resets(self, resets: list) -> None:
+        """Rows of the state table (and bias lists) of newly bound slots, staged through
+        two event-guarded pinned buffers; enqueued on the step's stream, so every update
+        of the slot's previous owner lands before and the owner's first step after."""
+        self._state_init()
+        nb = ops.LOGIT_BIAS_MAX
+        packed, nres, total = ops.pack_state_resets([r[:3] for r in resets])
+        n = packed.size + 2 * nres * nb
+        i = self._rst_idx
+        self._rst_idx ^= 1
+        if self._rst_ev[i] is not None:
+            self._rst_ev[i].synchronize()
+        if self._rst_pin[i] is None or self._rst_pin[i].numel() < n:
+            self._rst_pin[i] = _pinned(max(n, 1 << 16), torch.int32)
+        h = self._rst_pin[i]
+        hn = h.numpy()
+        hn[:packed.size] = packed
+        bi = hn[packed.size:packed.size + nres * nb].reshape(nres, nb)
+        bv = hn[packed.size + nres * nb:n].view(np.float32).reshape(nres, nb)
+        bi[:] = 0
+        bv[:] = 0.0
+        for j, r in enumerate(resets):
+            k = len(r[3])
+            bi[j, :k] = r[3]
+            bv[j, :k] = r[4]
+        if self.is_cuda:
+            d = h[:n].to(self.device, non_blocking=True)
+            ev = self._rst_ev[i] or torch.cuda.Event()
+            ev.record()
+            self._rst_ev[i] = ev
+        else:
+            d = h[:n].clone()
+        ops.logit_state_reset(self.p_state, d, nres, total)
+        for j, r in enumerate(resets):
+            if len(r[3]):
+                s, o = int(r[0]), packed.size + j * nb
+                self.p_bias_ids[s * nb:(s + 1) * nb].copy_(d[o:o + nb])
+                self.p_bias_vals[s * nb:(s + 1) * nb].copy_(d[o + nres * nb:o + nres * nb + nb].view(torch.float32))
+
+    @staticmethod
+    def _fill_proc_rows(pi: np.ndarray, pf: np.ndarray, samp: SamplingRows, n: int, rows: int) -> None:
+        """Host rows [0, n) from `samp`, padding rows [n, rows) plain (pi: [3, R], pf: [4, R])."""
+        pi[0, :n] = samp.slots
+        pi[1, :n] = np.maximum(samp.slots, 0) * ops.LOGIT_BIAS_MAX
+        pi[2, :n] = samp.bias_lens
+        pf[:, :n] = samp.pens
+        pi[0, n:rows] = -1
+        pi[1:, n:rows] = 0
+        pf[0, n:rows] = 1.0
+        pf[1:3, n:rows] = 0.0
+        pf[3, n:rows] = -np.inf
+
+    def _stage_proc(self, si: int, samp: SamplingRows, n: int, rows: int) -> None:
+        """Per-row processor parameters of a graph step -> g_pi / g_pf (rows >= n: plain)."""
+        R = self.g_OB
+        hi, hf = self.h_pis[si], self.h_pfs[si]
+        self._fill_proc_rows(hi.numpy().reshape(3, R), hf.numpy().reshape(4, R), samp, n, rows)
+        self.g_pi.view(-1).copy_(hi, non_blocking=True)
+        self.g_pf.view(-1).copy_(hf, non_blocking=True)
+
+    def _process_graph_rows(self, logits: torch.Tensor, rows: int) -> torch.Tensor:
+        out = self.p_scratch[:rows]
+        return ops.process_logits(logits, out, self.p_state, self.g_pi, self.g_pf, self.g_temp, self.p_bias_ids,
+                                  self.p_bias_vals)
+
+    def _proc_graph(self, key: tuple, mixed: bool):
+        """The processed form of a decode (mixed) graph, captured when a step first needs
+        it. Steps may still be running ahead (asynchronous scheduling), so the device is
+        drained first; the warm-up run and the capture see neutral inputs (padding rows,
+        no tracked slot) and the static buffers get their contents back afterwards."""
+        graphs = self.proc_mixed_graphs if mixed else self.proc_graphs
+        n, greedy = key
+        key = (n, greedy, self.p_state is not None)
+        g = graphs.get(key)
+        if g is not None:
+            return g
+        torch.cuda.synchronize()
+        body = (lambda: self._mixed_body(n, greedy, True)) if mixed else (lambda: self._decode_body(n, greedy, True))
+        keep = [self.g_int, self.g_out, self.g_pi] + ([self.m_int, self.m_lidx] if mixed else [])
+        saved = [t.clone() for t in keep]
+        with self._gc_held():
+            self._neutral_inputs(mixed)
+            self.g_pi[0].fill_(-1)
+            self.g_pi[2].zero_()
+            g = self._warm_and_capture([(key, body)], warm=1, error_mode="thread_local")[key]
+        for t, c in zip(keep, saved):
+            t.copy_(c)
+        torch.cuda.synchronize()
+        graphs[key] = g
+        log.info("captured the processed %s graph %s", "mixed-step" if mixed else "decode", key)
+        return g
+
+    # ---- capture choreography shared by the start-up graphs and the processed ones
+    @staticmethod
+    @contextlib.contextmanager
+    def _gc_held():
+        """An engine that was dropped earlier is a reference cycle: its graphs and their
+        pool live until the cycle collector runs. A collection in the middle of a
+        capture would destroy them inside the capturing region (graph destruction and
+        the pool's frees are not allowed there) and abort the process, so collect now
+        and hold automatic collections off until the last capture has ended."""
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            yield
+        finally:
+            if gc_was_enabled:
+                gc.enable()
+
+    def _neutral_inputs(self, mixed: bool) -> None:
+        if mixed:  # padding decode rows, an empty chunk (q = 0: no attention rows)
+            self.m_int.zero_()
+            self.m_slot.fill_(-1)
+            self.m_src.fill_(-1)
+            self.m_lidx.zero_()
+        else:      # padding rows (no KV writes, no attention work)
+            self.g_slot.fill_(-1)
+            self.g_src.fill_(-1)
+            self.g_sl.fill_(0)
+            self.g_ids.fill_(0)
+            self.g_pos.fill_(0)
+
+    def _warm_and_capture(self, bodies: list, warm: int, error_mode: str = "global") -> dict:
+        """bodies: [(key, fn)]. Every fn runs `warm` times on a side stream, then each is
+        captured into the shared graph pool. Returns {key: graph}."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _, fn in bodies:
+                for _ in range(warm):
+                    fn()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        out = {}
+        for key, fn in bodies:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode=error_mode):
+                fn()
+            out[key] = g
+        torch.cuda.synchronize()
+        return out
 
     # the first launches run under the generous peer-wait limit too (first-call RCCL
     # communicator setup of a subgroup, first-seen library GEMM shapes)
@@ -309,71 +514,24 @@ class ModelRunner:
     def capture_graphs(self):
         if not self.use_graphs or not self.graph_bs:
             return
-        # An engine that was dropped earlier is a reference cycle: its graphs and their
-        # pool live until the cycle collector runs. A collection in the middle of a
-        # capture would destroy them inside the capturing region (graph destruction and
-        # the pool's frees are not allowed there) and abort the process, so collect now
-        # and hold automatic collections off until the last capture has ended.
-        gc.collect()
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
+        with self._gc_held():
             self._capture_graphs()
-        finally:
-            if gc_was_enabled:
-                gc.enable()
 
     def _capture_graphs(self):
         torch.cuda.synchronize()
-        # neutral inputs: padding rows (no KV writes, no attention work)
-        self.g_slot.fill_(-1)
-        self.g_src.fill_(-1)
-        self.g_sl.fill_(0)
-        self.g_ids.fill_(0)
-        self.g_pos.fill_(0)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for bs in reversed(self.graph_bs):
-                for greedy in (True, False):
-                    for _ in range(2):
-                        self._decode_body(bs, greedy)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._graph_pool = torch.cuda.graph_pool_handle()
-        for bs in reversed(self.graph_bs):
-            for greedy in (True, False):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self._graph_pool):
-                    self._decode_body(bs, greedy)
-                self.graphs[(bs, greedy)] = g
-        torch.cuda.synchronize()
+        self._neutral_inputs(False)
+        bodies = [((bs, greedy), (lambda bs=bs, greedy=greedy: self._decode_body(bs, greedy)))
+                  for bs in reversed(self.graph_bs) for greedy in (True, False)]
+        self.graphs.update(self._warm_and_capture(bodies, warm=2))
         log.info("captured %d decode graphs (batch sizes %s)", len(self.graphs), self.graph_bs)
         if self.mixed_chunk > 0:
             self._capture_mixed()
 
     def _capture_mixed(self):
-        # neutral inputs: padding decode rows, an empty chunk (q = 0: no attention rows)
-        self.m_int.zero_()
-        self.m_slot.fill_(-1)
-        self.m_src.fill_(-1)
-        self.m_lidx.zero_()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for nb in reversed(self.mixed_bs):
-                for greedy in (True, False):
-                    for _ in range(2):
-                        self._mixed_body(nb, greedy)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        for nb in reversed(self.mixed_bs):
-            for greedy in (True, False):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self._graph_pool):
-                    self._mixed_body(nb, greedy)
-                self.mixed_graphs[(nb, greedy)] = g
-        torch.cuda.synchronize()
+        self._neutral_inputs(True)
+        bodies = [((nb, greedy), (lambda nb=nb, greedy=greedy: self._mixed_body(nb, greedy)))
+                  for nb in reversed(self.mixed_bs) for greedy in (True, False)]
+        self.mixed_graphs.update(self._warm_and_capture(bodies, warm=2))
         log.info("captured %d mixed-step graphs (decode rows %s + a %d-token chunk)", len(self.mixed_graphs),
                  self.mixed_bs, self.mixed_chunk)
 
@@ -415,6 +573,10 @@ class ModelRunner:
         ns = int(plan["num_seqs"])
         if T == 0:
             return (0, None, (None, None, None), None)
+        if samp is not None and samp.processed:
+            self._proc_init()
+            if samp.resets:
+                self._apply_resets(samp.resets)
         if self._warm_launches:
             self._warm_launches -= 1
             if self._warm_launches == 0:
@@ -497,6 +659,9 @@ class ModelRunner:
 
     def _execute_graph(self, plan, samp: Optional[SamplingRows], n: int, bs: int, src: Optional[np.ndarray]):
         B, W = self.g_B, self.g_W
+        greedy = samp is None or samp.all_greedy
+        proc = samp is not None and samp.processed
+        graph = self._proc_graph((bs, greedy), False) if proc else self.graphs[(bs, greedy)]
         si = self.g_stage_idx
         self.g_stage_idx ^= 1
         if self.g_stage_events[si] is not None:
@@ -519,13 +684,14 @@ class ModelRunner:
         bt[:n, :w] = plan["block_tables"].reshape(n, w)
         # ids..src (5*B) and the first bs rows of bt: one contiguous H2D copy
         self.g_int[:5 * B + bs * W].copy_(h_int[:5 * B + bs * W], non_blocking=True)
-        greedy = samp is None or samp.all_greedy
-        if not greedy:
+        if not greedy or proc:
             self._stage_sampling(si, samp, n)
+        if proc:
+            self._stage_proc(si, samp, n, bs)
         ev = self.g_stage_events[si] or torch.cuda.Event()
         ev.record()
         self.g_stage_events[si] = ev
-        self.graphs[(bs, greedy)].replay()
+        graph.replay()
         self._log_samples(n)
         if not self.is_driver:
             # no D2H to wait on; wait() still drains before the pinned inputs get rewritten
@@ -565,6 +731,9 @@ class ModelRunner:
         chunk's q rows at [B, B + q) of the static input buffers."""
         B, W, C = self.g_B, self.g_W, self.mixed_chunk
         n = int(plan["num_sample"])
+        greedy = samp is None or samp.all_greedy
+        proc = samp is not None and samp.processed
+        graph = self._proc_graph((nb, greedy), True) if proc else self.mixed_graphs[(nb, greedy)]
         si = self.g_stage_idx
         self.g_stage_idx ^= 1
         if self.g_stage_events[si] is not None:
@@ -573,13 +742,14 @@ class ModelRunner:
                            self.h_mlidx[si].numpy())
         self.m_int.copy_(self.h_mints[si], non_blocking=True)
         self.m_lidx[:nb + 1].copy_(self.h_mlidx[si][:nb + 1], non_blocking=True)
-        greedy = samp is None or samp.all_greedy
-        if not greedy:
+        if not greedy or proc:
             self._stage_sampling(si, samp, n)
+        if proc:
+            self._stage_proc(si, samp, n, nb + 1)
         ev = self.g_stage_events[si] or torch.cuda.Event()
         ev.record()
         self.g_stage_events[si] = ev
-        self.mixed_graphs[(nb, greedy)].replay()
+        graph.replay()
         self.mixed_replays += 1
         self._log_samples(n)
         if not self.is_driver:
@@ -658,8 +828,11 @@ class ModelRunner:
                 # the successor's decode rows substitute their ids from this rank's
                 # g_out_tok exactly as after a graph step
                 on_dev = self._async_ok(S, plan)
-                if on_dev:
+                # a processed step is sampled on every rank even when its tokens stay
+                # unused here: the sampling advances this rank's token statistics
+                if on_dev or (samp is not None and samp.processed):
                     tok, _ = self._sample(logits, samp)
+                if on_dev:
                     self.g_out_tok[:S].copy_(tok[:S])
                     self._log_samples(S)
                 # an event of THIS step: a follower that queued its successor waits
@@ -675,7 +848,57 @@ class ModelRunner:
             return self._record_out(S, tok, lp, hid, on_dev)
         return (S, hid, (tok.numpy().astype(np.int32), lp.numpy().astype(np.float32), hid), None)
 
+    def _sample_processed(self, logits: torch.Tensor, samp: SamplingRows):
+        """The processed form of an eager step's sampling: process_logits -> the sampler
+        on the fp32 scratch -> logit_state_update, parameters staged like _sample's."""
+        n, V = logits.shape
+        pi, pf = np.empty((3, n), np.int32), np.empty((4, n), np.float32)
+        self._fill_proc_rows(pi, pf, samp, n, n)
+        if self.is_cuda:
+            i = self._es_idx
+            self._es_idx ^= 1
+            if self._es_ev[i] is not None:
+                self._es_ev[i].synchronize()
+            if self._es_pin[i] is None or self._es_pin[i][1].numel() < n or len(self._es_pin[i]) < 5:
+                m = max(n, 64)
+                self._es_pin[i] = (_pinned(2 * m, torch.float32), _pinned(m, torch.int32), _pinned(m, torch.int64),
+                                   _pinned(3 * m, torch.int32), _pinned(4 * m, torch.float32))
+            hf, hk, hs, hpi, hpf = self._es_pin[i]
+            f = hf.numpy()
+            f[:n] = samp.temps
+            f[n:2 * n] = samp.top_ps
+            hk.numpy()[:n] = samp.top_ks
+            hs.numpy()[:n] = samp.seeds
+            hpi.numpy()[:3 * n] = pi.reshape(-1)
+            hpf.numpy()[:4 * n] = pf.reshape(-1)
+            dev_f = hf[:2 * n].to(self.device, non_blocking=True).view(2, n)
+            topk = hk[:n].to(self.device, non_blocking=True)
+            seeds = hs[:n].to(self.device, non_blocking=True)
+            d_pi = hpi[:3 * n].to(self.device, non_blocking=True).view(3, n)
+            d_pf = hpf[:4 * n].to(self.device, non_blocking=True).view(4, n)
+            ev = self._es_ev[i] or torch.cuda.Event()
+            ev.record()
+            self._es_ev[i] = ev
+            gen = None
+        else:
+            dev_f = torch.from_numpy(np.stack([samp.temps, samp.top_ps]).astype(np.float32))
+            topk = torch.from_numpy(samp.top_ks.astype(np.int32))
+            seeds = torch.from_numpy(samp.seeds.astype(np.int64))
+            d_pi, d_pf = torch.from_numpy(pi), torch.from_numpy(pf)
+            gen = torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
+        out = ops.process_logits(logits, ops.process_scratch(n, V, logits.device), self.p_state, d_pi, d_pf,
+                                 dev_f[0], self.p_bias_ids, self.p_bias_vals)
+        if samp.all_greedy:
+            tok, lp = ops.argmax_logprob(out)
+        else:
+            tok, lp = ops.sample_tokens(out, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
+        if self.p_state is not None:
+            ops.logit_state_update(self.p_state, d_pi[0], tok, n)
+        return tok, lp
+
     def _sample(self, logits: torch.Tensor, samp: Optional[SamplingRows]):
+        if samp is not None and samp.processed:
+            return self._sample_processed(logits, samp)
         if samp is None or samp.all_greedy:
             tok, lp = ops.argmax_logprob(logits)
         elif self.is_cuda:
@@ -690,7 +913,7 @@ class ModelRunner:
             if self._es_pin[i] is None or self._es_pin[i][1].numel() < n:
                 m = max(n, 64)
                 self._es_pin[i] = (_pinned(2 * m, torch.float32), _pinned(m, torch.int32), _pinned(m, torch.int64))
-            hf, hk, hs = self._es_pin[i]
+            hf, hk, hs = self._es_pin[i][:3]
             f = hf.numpy()
             f[:n] = samp.temps
             f[n:2 * n] = samp.top_ps

@@ -12,6 +12,8 @@ from .linear import skinny_linear, PendingSum
 from .attention import (decode_attention, decode_attention_fused, prefill_attention, decode_attention_ref,
                         prefill_attention_ref, choose_num_splits)
 from .sampling import argmax_logprob, sample_tokens, argmax_logprob_ref, segment_sum, subst_tokens
+from .sampling import (process_logits, process_scratch, logit_state_alloc, logit_state_cells, logit_state_reset,
+                       logit_state_update, pack_state_resets, LOGIT_BIAS_MAX)
 from .embedding import embed_gather, mean_l2norm_rows
 from .moe import (moe_topk_softmax, moe_route, moe_route_norm, moe_align, moe_forward_ref, fused_moe, ep_plan,
                   ep_scatter, ep_combine)
@@ -23,6 +25,8 @@ __all__ = [
     "RotaryCache", "rope_cache", "rope_cache_ref", "build_cos_sin",
     "decode_attention", "decode_attention_fused", "prefill_attention", "decode_attention_ref", "prefill_attention_ref", "choose_num_splits",
     "argmax_logprob", "sample_tokens", "argmax_logprob_ref", "segment_sum", "subst_tokens",
+    "process_logits", "process_scratch", "logit_state_alloc", "logit_state_cells", "logit_state_reset",
+    "logit_state_update", "pack_state_resets", "LOGIT_BIAS_MAX",
     "embed_gather", "mean_l2norm_rows",
     "moe_topk_softmax", "moe_route", "moe_route_norm", "moe_align", "moe_forward_ref", "fused_moe", "ep_plan", "ep_scatter", "ep_combine",
     "native_available",

@@ -130,6 +130,165 @@ def _sample_workspace(device, B: int) -> torch.Tensor:
     return wss[-1]
 
 
+# ---------------------------------------------------------------------------
+# Logit processors (csrc/kernels/logit_proc.hip): repetition / frequency / presence
+# penalties, logit_bias and min_p, applied to a step's logits rows in front of the
+# samplers, and the per-slot token statistics they read. On CPU tensors the same
+# arithmetic runs in numpy (one fp32 rounding per step, as the kernels).
+# ---------------------------------------------------------------------------
+LOGIT_BIAS_MAX = 128       # logit_bias entries per request (LP_BIAS_MAX)
+LOGIT_COUNT_MAX = 0x7FFF   # a cell's generated-count saturates here
+LOGIT_PROMPT_FLAG = 0x8000  # cell bit 15: the token occurs in the prompt
+_LOGIT_CHUNK = 4096        # LP_CHUNK: tokens per workgroup
+
+
+def logit_state_alloc(num_slots: int, vocab: int, device) -> torch.Tensor:
+    """The zeroed state table: one row of `vocab` 16-bit cells per engine slot (the bits
+    are unsigned: view the numpy array as uint16)."""
+    return torch.zeros(num_slots, vocab, dtype=torch.int16, device=device)
+
+
+def logit_state_cells(prompt_ids, generated_ids):
+    """Unique token ids of a sequence and their cells (prompt flag | saturating count of
+    the generated tokens), as two int32 arrays: what logit_state_reset scatters."""
+    import numpy as np
+    gen = np.asarray(generated_ids, dtype=np.int64).reshape(-1)
+    pro = np.unique(np.asarray(prompt_ids, dtype=np.int64).reshape(-1))
+    gu, gc = np.unique(gen, return_counts=True)
+    ids = np.union1d(pro, gu)
+    cells = np.zeros(ids.shape[0], np.int64)
+    cells[np.searchsorted(ids, pro)] |= LOGIT_PROMPT_FLAG
+    cells[np.searchsorted(ids, gu)] |= np.minimum(gc, LOGIT_COUNT_MAX)
+    return ids.astype(np.int32), cells.astype(np.int32)
+
+
+def pack_state_resets(resets):
+    """[(slot, ids, cells)] -> one int32 array [3 nres descriptors | ids | cells] and
+    (nres, total): the staging layout of logit_state_reset."""
+    import numpy as np
+    nres = len(resets)
+    total = sum(len(r[1]) for r in resets)
+    buf = np.empty(3 * nres + 2 * total, np.int32)
+    off = 0
+    for j, (slot, ids, cells) in enumerate(resets):
+        n = len(ids)
+        buf[3 * j:3 * j + 3] = (slot, off, n)
+        buf[3 * nres + off:3 * nres + off + n] = ids
+        buf[3 * nres + total + off:3 * nres + total + off + n] = cells
+        off += n
+    return buf, nres, total
+
+
+def logit_state_reset(state: torch.Tensor, packed: torch.Tensor, nres: int, total: int) -> None:
+    """Zero the rows of `nres` slots and scatter their cells; `packed` (int32, on the
+    state's device) has the layout of pack_state_resets. Two resets of one call never
+    name the same slot."""
+    S, V = state.shape
+    assert packed.dtype == torch.int32 and packed.numel() >= 3 * nres + 2 * total and state.is_contiguous()
+    if nres == 0:
+        return
+    if not use_native(state):
+        st = state.numpy().view("uint16")
+        p = packed.numpy()
+        for j in range(nres):
+            slot, off, n = (int(v) for v in p[3 * j:3 * j + 3])
+            if not 0 <= slot < S:
+                continue
+            st[slot] = 0
+            ids = p[3 * nres + off:3 * nres + off + n]
+            st[slot, ids] = p[3 * nres + total + off:3 * nres + total + off + n].astype("uint16")
+        return
+    base = packed.data_ptr()
+    kernels().logit_state_reset(state.data_ptr(), S, V, base, nres, base + 12 * nres, base + 12 * nres + 4 * total,
+                                total, stream_ptr())
+
+
+def logit_state_update(state: torch.Tensor, slots: torch.Tensor, toks: torch.Tensor, n: int) -> None:
+    """count[slots[i]][toks[i]] += 1 (saturating) for i < n with slots[i] >= 0; int32 inputs."""
+    S, V = state.shape
+    assert slots.dtype == toks.dtype == torch.int32 and slots.numel() >= n and toks.numel() >= n
+    if not use_native(state):
+        st = state.numpy().view("uint16")
+        for s, t in zip(slots[:n].tolist(), toks[:n].tolist()):
+            if 0 <= s < S and 0 <= t < V and (st[s, t] & LOGIT_COUNT_MAX) < LOGIT_COUNT_MAX:
+                st[s, t] += 1
+        return
+    kernels().logit_state_update(state.data_ptr(), S, V, slots.data_ptr(), toks.data_ptr(), n, stream_ptr())
+
+
+_PROC_WS = {}
+
+
+def _proc_ws(device, rows: int, V: int) -> torch.Tensor:
+    """Per-chunk row maxima of the min_p pass; grown on demand, earlier ones kept alive
+    for captured graphs."""
+    need = rows * ((V + _LOGIT_CHUNK - 1) // _LOGIT_CHUNK)
+    wss = _PROC_WS.setdefault((device.type, device.index), [])
+    if not wss or wss[-1].numel() < need:
+        wss.append(torch.empty(max(need, 64 * 32), dtype=torch.float32, device=device))
+    return wss[-1]
+
+
+def process_scratch(rows: int, V: int, device) -> torch.Tensor:
+    """An fp32 [rows, V] scratch for process_logits whose rows start 16-byte aligned."""
+    return torch.empty(rows, (V + 3) & ~3, dtype=torch.float32, device=device)[:, :V]
+
+
+def process_logits(logits: torch.Tensor, out: torch.Tensor, state: Optional[torch.Tensor], pi: torch.Tensor,
+                   pf: torch.Tensor, temps: torch.Tensor, bias_ids: Optional[torch.Tensor] = None,
+                   bias_vals: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = processed fp32 logits of row i (bf16 or fp32 `logits`, any row stride).
+    pi: int32 [3, R] = slot (-1: no history) | offset into bias_ids / bias_vals | number
+    of bias entries; pf: fp32 [4, R] = repetition | frequency | presence penalty |
+    ln(min_p) (-inf: off); temps: fp32 [>= rows] (min_p applies where temps > 0); R >= rows."""
+    rows, V = logits.shape
+    R = pi.shape[1]
+    assert pi.dtype == torch.int32 and pf.dtype == torch.float32 and temps.dtype == torch.float32
+    assert pi.shape[0] == 3 and tuple(pf.shape) == (4, R) and R >= rows and temps.numel() >= rows
+    assert pi.is_contiguous() and pf.is_contiguous() and temps.is_contiguous()
+    assert out.dtype == torch.float32 and tuple(out.shape) == (rows, V) and out.stride(1) == 1 and logits.stride(1) == 1
+    assert state is None or (state.shape[1] == V and state.is_contiguous())
+    cap = 0 if bias_ids is None else min(bias_ids.numel(), bias_vals.numel())
+    if not use_native(logits):
+        _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals)
+        return out
+    assert logits.dtype in (torch.bfloat16, torch.float32)
+    ws = _proc_ws(logits.device, rows, V)
+    kernels().process_logits(logits.data_ptr(), 1 if logits.dtype == torch.float32 else 0, logits.stride(0),
+                             out.data_ptr(), out.stride(0), rows, V, ptr(state),
+                             0 if state is None else state.shape[0], pi.data_ptr(), pf.data_ptr(), R,
+                             temps.data_ptr(), ptr(bias_ids), ptr(bias_vals), cap, ws.data_ptr(), stream_ptr())
+    return out
+
+
+def _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals) -> None:
+    import numpy as np
+    f32 = np.float32
+    rows, V = logits.shape
+    x_all = logits.float().numpy()
+    o = out.numpy()
+    pin, pfn, tn = pi.numpy(), pf.numpy(), temps.numpy()
+    st = state.numpy().view("uint16") if state is not None else None
+    with np.errstate(all="ignore"):
+        for i in range(rows):
+            x = x_all[i].astype(f32)
+            slot, boff, blen = int(pin[0, i]), int(pin[1, i]), int(pin[2, i])
+            r, f, p, lm = f32(pfn[0, i]), f32(pfn[1, i]), f32(pfn[2, i]), f32(pfn[3, i])
+            cell = st[slot] if (st is not None and 0 <= slot < st.shape[0]) else np.zeros(V, np.uint16)
+            c = (cell & LOGIT_COUNT_MAX).astype(np.int32)
+            x = np.where(cell != 0, np.where(x > 0, x / r, x * r), x).astype(f32)
+            x = (x - (f * c.astype(f32)).astype(f32)).astype(f32)
+            x = np.where(c > 0, x - p, x).astype(f32)
+            if blen > 0:
+                ids = bias_ids.numpy()[boff:boff + blen]
+                x[ids] = x[ids] + bias_vals.numpy()[boff:boff + blen].astype(f32)
+            t = f32(tn[i])
+            if t > 0 and lm > -np.inf:
+                y = (x * (f32(1) / t)).astype(f32)
+                x = np.where(y < f32(y.max() + lm), f32(-np.inf), x).astype(f32)
+            o[i] = x
+
+
 def segment_sum(hidden: torch.Tensor, cu: torch.Tensor, out: torch.Tensor,
                 out_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[rows[s]] += sum(hidden[cu[s]:cu[s+1]]) (fp32)."""

@@ -32,7 +32,7 @@ from ..core.errors import ApiError, ApiInternal, ApiValidationError, ConfigError
 from ..core.types import Priority
 from ..core.wire import (ChatChoice, ChatMessage, ChatRequest, ChatResponse, EmbeddingData, EmbeddingsRequest,
                          EmbeddingsResponse, FinishReason, GenerateChoice, GenerateRequest, GenerateResponse, Role,
-                         TokenEvent, Usage)
+                         PROCESSOR_FIELDS, TokenEvent, Usage)
 from ..engine.request import RequestType, SamplingParams
 from ..obs import trace
 from .orchestrator import InferenceServer, ServerRequest, sse_chunk
@@ -93,9 +93,34 @@ async def _body(request: web.Request) -> bytes:
     return await request.read()
 
 
-def _params(max_tokens, temperature, top_p, stop, seed=None, ignore_eos=False, logprobs=False) -> SamplingParams:
-    return SamplingParams(max_tokens=int(max_tokens), temperature=float(temperature), top_p=float(top_p),
-                          stop=list(stop), seed=seed, ignore_eos=ignore_eos, logprobs=logprobs)
+def _params(max_tokens, temperature, top_p, stop, seed=None, ignore_eos=False, logprobs=False,
+            req=None) -> SamplingParams:
+    sp = SamplingParams(max_tokens=int(max_tokens), temperature=float(temperature), top_p=float(top_p),
+                        stop=list(stop), seed=seed, ignore_eos=ignore_eos, logprobs=logprobs)
+    if req is not None:  # the sampling extensions of a parsed Generate / Chat request
+        sp.top_k = min(int(req.top_k), 2**31 - 1)
+        sp.min_p, sp.repetition_penalty = float(req.min_p), float(req.repetition_penalty)
+        sp.presence_penalty, sp.frequency_penalty = float(req.presence_penalty), float(req.frequency_penalty)
+        sp.logit_bias = dict(req.logit_bias)
+    return sp
+
+
+def _validate_processors(srv: InferenceServer, req) -> None:
+    """Ranges of the sampling extensions (400, `Invalid parameter '<field>': <reason>`);
+    a server that decodes speculatively accepts plain requests only."""
+    res = srv.validator.check_processors(req.min_p, req.repetition_penalty, req.presence_penalty,
+                                         req.frequency_penalty, list(req.logit_bias.keys()),
+                                         list(req.logit_bias.values()),
+                                         int(srv.model_info.get("vocab_size", 0) or 0))
+    InferenceServer._raise_validation(res)
+    spec = getattr(srv.cfg, "spec", None)
+    speculating = spec is not None and spec.draft_model and spec.num_speculative_tokens > 0
+    if speculating:
+        for name, neutral in (("min_p", 0.0), ("repetition_penalty", 1.0), ("presence_penalty", 0.0),
+                              ("frequency_penalty", 0.0), ("logit_bias", {})):
+            if getattr(req, name) != neutral:
+                raise ApiValidationError(ValidationError.invalid_parameter(
+                    name, "is not supported together with speculative decoding"))
 
 
 async def _await_result(request: web.Request, srv: InferenceServer, sreq: ServerRequest) -> ServerRequest:
@@ -194,8 +219,10 @@ async def handle_generate(request: web.Request) -> web.StreamResponse:
     with trace.span("validate", endpoint="/generate"):
         req = GenerateRequest.parse(await _body(request))
         srv.validate_generate(req.prompt, req.max_tokens, req.temperature, req.top_p)
+        _validate_processors(srv, req)
     ids = srv.encode(req.prompt)
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req.logprobs)
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req.logprobs,
+                 req=req)
     sreq = await srv.aadmit(RequestType.Generate, ids, sp, req.priority if req.priority is not None else Priority.Normal,
                      stream=req.stream, sse_native=req.stream)
     if req.stream:
@@ -210,8 +237,9 @@ async def handle_chat(request: web.Request) -> web.StreamResponse:
     with trace.span("validate", endpoint="/chat"):
         req = ChatRequest.parse(await _body(request))
         srv.validate_chat([m.content for m in req.messages], req.max_tokens, req.temperature, req.top_p)
+        _validate_processors(srv, req)
     ids = srv.encode(srv.tokenizer.apply_chat_template(req.messages))
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos)
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req=req)
     sreq = await srv.aadmit(RequestType.Chat, ids, sp, Priority.Normal, stream=req.stream, sse_native=req.stream)
     if req.stream:
         return await _sse(request, srv, sreq)
@@ -341,14 +369,16 @@ async def handle_v1_completions(request: web.Request) -> web.StreamResponse:
     p = d.get("prompt")
     if isinstance(p, list) and len(p) == 1 and isinstance(p[0], str):
         p = p[0]
-    body = {k: v for k, v in d.items() if k in ("max_tokens", "temperature", "top_p", "stream", "seed", "priority")}
+    body = {k: v for k, v in d.items()
+            if k in ("max_tokens", "temperature", "top_p", "stream", "seed", "priority") + PROCESSOR_FIELDS}
     body["prompt"] = p if p is not None else None
     if body["prompt"] is None:
         body.pop("prompt")
     body["stop_sequences"] = _oa_stop(d)
     req = GenerateRequest.parse(body)
     srv.validate_generate(req.prompt, req.max_tokens, req.temperature, req.top_p)
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed)
+    _validate_processors(srv, req)
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req=req)
     sreq = await srv.aadmit(RequestType.Generate, srv.encode(req.prompt), sp,
                      req.priority if req.priority is not None else Priority.Normal, stream=req.stream)
     created = int(time.time())
@@ -374,13 +404,15 @@ async def handle_v1_chat(request: web.Request) -> web.StreamResponse:
     d = json.loads(await _body(request) or b"{}")
     if not isinstance(d, dict):
         raise ValidationError.invalid_json("invalid type: expected a JSON object")
-    body = {k: v for k, v in d.items() if k in ("messages", "max_tokens", "temperature", "top_p", "stream", "seed")}
+    body = {k: v for k, v in d.items()
+            if k in ("messages", "max_tokens", "temperature", "top_p", "stream", "seed") + PROCESSOR_FIELDS}
     if "max_completion_tokens" in d and "max_tokens" not in body:
         body["max_tokens"] = d["max_completion_tokens"]
     body["stop_sequences"] = _oa_stop(d)
     req = ChatRequest.parse(body)
     srv.validate_chat([m.content for m in req.messages], req.max_tokens, req.temperature, req.top_p)
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed)
+    _validate_processors(srv, req)
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req=req)
     sreq = await srv.aadmit(RequestType.Chat, srv.encode(srv.tokenizer.apply_chat_template(req.messages)), sp,
                      Priority.Normal, stream=req.stream)
     created = int(time.time())

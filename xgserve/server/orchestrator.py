@@ -597,6 +597,10 @@ class InferenceServer:
             if o.error:
                 self._finalize(sreq)
                 self.metrics.record_error(o.error_code or "inference_failed")
+                if o.error_code == "invalid_parameter":  # engine-side rejection of sampling parameters
+                    field, _, reason = o.error.partition(": ")
+                    self._fail(sreq, ApiValidationError(ValidationError.invalid_parameter(field, reason)))
+                    continue
                 self._fail(sreq, ApiInternal(o.error.removeprefix("Inference failed: ")
                                              if o.error_code == "inference_failed" else o.error,
                                              code=o.error_code or "inference_failed"))

@@ -147,7 +147,7 @@ class EngineLoop:
         self._wake.set()
 
     def _drain(self, outs: list) -> None:
-        from ..engine.request import RequestOutput, RequestType, SamplingParams
+        from ..engine.request import RequestOutput, RequestType, SamplingParams, UnsupportedSampling
         while True:
             try:
                 cmd = self._inbox.get_nowait()
@@ -160,6 +160,9 @@ class EngineLoop:
                     self._sse.add(rid)
                 try:
                     self.engine.add_request(rid, prompt_ids, params, prio, RequestType(kind))
+                except UnsupportedSampling as e:  # the engine cannot honour the parameters: 400
+                    outs.append(RequestOutput(rid, [], "", True, "error", prompt_tokens=len(prompt_ids),
+                                              error=str(e), error_code="invalid_parameter"))
                 except Exception as e:  # per-request rejection, never fatal
                     outs.append(RequestOutput(rid, [], "", True, "error", prompt_tokens=len(prompt_ids),
                                               error=f"Inference failed: {e}", error_code="inference_failed"))
