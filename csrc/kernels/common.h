@@ -67,6 +67,15 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
+// y = logit / T, rounded to fp32 on its own. Every pass of both samplers and top_logprobs
+// must see the same y: a product contracted into `M - y` (one fma) in one kernel and
+// rounded in another puts a token next to a bin edge into different bins in the two, and
+// the draw then drops a token the histograms counted as kept.
+__device__ __forceinline__ float scaled_logit(float x, float it) {
+#pragma clang fp contract(off)
+  return x * it;
+}
+
 // ---- wave / block reductions (wave64) -------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -46,6 +46,11 @@ int argmax_ws_floats_per_row();
 void sample_tokens(const void*, int, int64_t, int, int, const float*, const float*, const int32_t*, const uint64_t*,
                    uint64_t, int32_t*, float*, void*, hipStream_t);
 size_t sample_ws_row_bytes();
+int top_logprobs(const void*, int, int64_t, int, int, const int32_t*, int, const float*, int, int32_t*, float*, void*,
+                 int*, hipStream_t);
+int top_logprobs_max();
+int top_logprobs_parts();
+int top_logprobs_ws_words();
 void segment_sum(const uint16_t*, int, const int32_t*, const int32_t*, float*, int, hipStream_t);
 void subst_tokens(int32_t*, const int32_t*, const int32_t*, int, hipStream_t);
 int process_logits(const void*, int, int64_t, float*, int64_t, int, int, const uint16_t*, int, const int32_t*,
@@ -209,6 +214,24 @@ PYBIND11_MODULE(_kernels, m) {
      py::arg("top_ps"), py::arg("top_ks"), py::arg("seeds"), py::arg("step"), py::arg("tok"), py::arg("lp"),
      py::arg("st"), py::arg("ws") = 0, py::arg("ws_rows") = 0);
   m.def("sample_ws_row_bytes", []() { return static_cast<int64_t>(xgk::sample_ws_row_bytes()); });
+  // top-K tokens and log-probabilities of the asked rows (top_logprobs.hip). rows: int32 [n]
+  // logits-row indices (0: rows 0..n-1); temps: fp32 indexed by logits row; ws / tickets
+  // (optional): the split-row form -- n x top_logprobs_ws_words() u64 and n zeroed ints
+  m.def("top_logprobs", [](uintptr_t logits, int is_f32, int64_t stride, int num_rows, int V, uintptr_t rows, int n,
+                           uintptr_t temps, int K, uintptr_t out_ids, uintptr_t out_lps, uintptr_t st, uintptr_t ws,
+                           uintptr_t tickets, int ws_rows) {
+    if (rows == 0 && n > num_rows) throw std::invalid_argument("top_logprobs: n exceeds the logits rows");
+    if (ws != 0 && ws_rows < n) throw std::invalid_argument("top_logprobs: workspace holds fewer rows than n");
+    if ((ws != 0) != (tickets != 0)) throw std::invalid_argument("top_logprobs: ws and tickets go together");
+    check(xgk::top_logprobs(P<const void>(logits), is_f32, stride, num_rows, V, P<const int32_t>(rows), n,
+                            P<const float>(temps), K, P<int32_t>(out_ids), P<float>(out_lps), P<void>(ws),
+                            P<int>(tickets), S(st)),
+          "top_logprobs");
+  }, py::arg("logits"), py::arg("is_f32"), py::arg("stride"), py::arg("num_rows"), py::arg("V"), py::arg("rows"),
+     py::arg("n"), py::arg("temps"), py::arg("K"), py::arg("out_ids"), py::arg("out_lps"), py::arg("st"),
+     py::arg("ws") = 0, py::arg("tickets") = 0, py::arg("ws_rows") = 0);
+  m.def("top_logprobs_max", &xgk::top_logprobs_max);
+  m.def("top_logprobs_ws_words", &xgk::top_logprobs_ws_words);
   m.def("gemm_w8", [](uintptr_t x, int M, int K, uintptr_t w, uintptr_t scale, int N, uintptr_t part, uintptr_t out,
                       int splits, int mode, int cfg, uintptr_t st, int fmt) {
     check(xgk::gemm_w8(P<const uint16_t>(x), M, K, P<const uint8_t>(w), P<const float>(scale), N, P<float>(part),

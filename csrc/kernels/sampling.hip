@@ -126,15 +126,7 @@ __global__ void __launch_bounds__(1024) argmax_kernel(const T* __restrict__ logi
 // Gumbel-max sampling with optional top-k / top-p thresholds.
 // temps[row] <= 0 means greedy for that row.
 // --------------------------------------------------------------------------
-// y = logit / T, rounded to fp32 on its own. Every pass of both samplers must see the
-// same y: a product contracted into `M - y` (one fma) in one kernel and rounded in
-// another puts a token next to a bin edge into different bins in the two, and the draw
-// then drops a token the histograms counted as kept.
-__device__ __forceinline__ float scaled_logit(float x, float it) {
-#pragma clang fp contract(off)
-  return x * it;
-}
-
+// y = logit / T is common.h's scaled_logit in every pass of both samplers.
 template <typename T>
 __device__ float block_reduce_max(float v, float* sh) {
   v = wave_max(v);

@@ -175,6 +175,8 @@ PYBIND11_MODULE(_runtime, m) {
               const std::vector<uint64_t>& ids, const std::vector<float>& vals, uint64_t vocab) {
              return vres(v.check_processors(min_p, rp, pp, fp, ids, vals, vocab));
            })
+      .def("check_top_logprobs",
+           [](const RequestValidator& v, long long n) { return vres(v.check_top_logprobs(n)); })
       .def("config", &RequestValidator::config)
       .def("set_config", &RequestValidator::set_config);
 

@@ -149,6 +149,13 @@ ValidationResult RequestValidator::check_processors(float min_p, float repetitio
   return ValidationResult{};
 }
 
+ValidationResult RequestValidator::check_top_logprobs(long long n) const {
+  if (n < 0 || n > kMaxTopLogprobs)
+    return invalid_param("top_logprobs", "must be an integer between 0 and " +
+                                             std::to_string(kMaxTopLogprobs) + ", got " + std::to_string(n));
+  return ValidationResult{};
+}
+
 ValidationResult RequestValidator::validate_generate(const std::string& prompt, size_t max_tokens,
                                                      float temperature, float top_p) const {
   if (is_blank_utf8(prompt)) return empty_prompt();

@@ -83,6 +83,10 @@ class RequestValidator {
                                     float frequency_penalty, const std::vector<uint64_t>& bias_ids,
                                     const std::vector<float>& bias_values, uint64_t vocab_size) const;
 
+  // top_logprobs (alternatives per token): an integer in [0, kMaxTopLogprobs].
+  static constexpr long long kMaxTopLogprobs = 20;
+  ValidationResult check_top_logprobs(long long n) const;
+
   const ValidatorConfig& config() const { return cfg_; }
   void set_config(const ValidatorConfig& c) { cfg_ = c; }
 

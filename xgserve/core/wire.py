@@ -193,6 +193,27 @@ def _processors(d: dict) -> dict:
     return out
 
 
+TOP_LOGPROBS_MAX = 20
+_I64 = 2**63 - 1
+
+
+def top_logprobs_field(d: dict, name: str = "top_logprobs") -> int:
+    """`top_logprobs` (or the completions alias' integer `logprobs`): an integer; its range
+    is the validator's (RequestValidator.check_top_logprobs), so values are only brought
+    into what the binding can carry."""
+    v = d.get(name)
+    if v is None:
+        return 0
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValidationError.invalid_parameter(name, f"must be an integer between 0 and {TOP_LOGPROBS_MAX}")
+    return max(-_I64, min(_I64, v))
+
+
+def _logprobs_flag(d: dict) -> bool:
+    v = d.get("logprobs", False)
+    return v if isinstance(v, bool) else False
+
+
 PROCESSOR_FIELDS = ("top_k", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias")
 
 
@@ -211,6 +232,7 @@ class GenerateRequest:
     # extensions (not in the reference wire format; ignored by it)
     seed: Optional[int] = None
     logprobs: bool = False
+    top_logprobs: int = 0
     ignore_eos: bool = False
     top_k: int = 0
     min_p: float = 0.0
@@ -233,7 +255,7 @@ class GenerateRequest:
             except ValueError as e:
                 raise ValidationError.invalid_json(str(e))
         return cls(prompt=prompt, priority=pr, seed=_opt_int(d, "seed"),
-                   logprobs=bool(d.get("logprobs", False)) if isinstance(d.get("logprobs", False), bool) else False,
+                   logprobs=_logprobs_flag(d), top_logprobs=top_logprobs_field(d),
                    ignore_eos=d.get("ignore_eos") is True, **s, **_processors(d))
 
 
@@ -260,6 +282,8 @@ class ChatRequest:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logit_bias: Dict[int, float] = field(default_factory=dict)
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     @classmethod
     def parse(cls, body: Union[bytes, str, dict]) -> "ChatRequest":
@@ -270,7 +294,7 @@ class ChatRequest:
             raise ValidationError.invalid_json("invalid type for `messages`: expected a sequence")
         msgs = [ChatMessage.from_dict(m) for m in d["messages"]]
         return cls(messages=msgs, seed=_opt_int(d, "seed"), ignore_eos=d.get("ignore_eos") is True,
-                   **_sampling(d), **_processors(d))
+                   logprobs=_logprobs_flag(d), top_logprobs=top_logprobs_field(d), **_sampling(d), **_processors(d))
 
 
 @dataclass
@@ -458,10 +482,17 @@ class TokenEvent:
     usage: Optional[Usage] = None
     message: Optional[str] = None
     code: Optional[str] = None
+    # extension: the alternatives of the event's (last) token, [{"token", "token_id", "logprob"}];
+    # serialised only when asked for, so every other event stays byte-identical
+    top_logprobs: Optional[List[dict]] = None
+    # not serialised: (token id, logprob, [(id, logprob)] or None) of every token the event
+    # covers, for the OpenAI aliases' per-chunk logprobs objects
+    detail: Optional[list] = None
 
     @classmethod
-    def tok(cls, token: str, index: int, logprob: Optional[float] = None) -> "TokenEvent":
-        return cls("token", token=token, index=index, logprob=logprob)
+    def tok(cls, token: str, index: int, logprob: Optional[float] = None,
+            top_logprobs: Optional[List[dict]] = None) -> "TokenEvent":
+        return cls("token", token=token, index=index, logprob=logprob, top_logprobs=top_logprobs)
 
     @classmethod
     def done(cls, finish_reason: FinishReason, usage: Usage) -> "TokenEvent":
@@ -476,6 +507,8 @@ class TokenEvent:
             d = {"type": "token", "token": self.token, "index": self.index}
             if self.logprob is not None:  # skip_serializing_if = "Option::is_none"
                 d["logprob"] = self.logprob
+            if self.top_logprobs is not None:
+                d["top_logprobs"] = self.top_logprobs
             return d
         if self.type == "done":
             return {"type": "done", "finish_reason": self.finish_reason.value,
@@ -486,7 +519,7 @@ class TokenEvent:
     def from_dict(cls, d: dict) -> "TokenEvent":
         t = d["type"]
         if t == "token":
-            return cls.tok(d["token"], d["index"], d.get("logprob"))
+            return cls.tok(d["token"], d["index"], d.get("logprob"), d.get("top_logprobs"))
         if t == "done":
             return cls.done(FinishReason(d["finish_reason"]), Usage.from_dict(d["usage"]))
         if t == "error":

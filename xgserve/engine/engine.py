@@ -220,6 +220,7 @@ class LLMEngine:
         self.slot_track = np.full(ns, -1, np.int32)
         self.slot_blen = np.zeros(ns, np.int32)
         self.slot_proc = np.zeros(ns, bool)
+        self.slot_topn = np.zeros(ns, np.int32)  # top_logprobs entries the slot's owner asked for
         self._resets: Dict[int, tuple] = {}  # slot -> state reset awaiting the next processed step
         self._deferred = None  # (plan, toks, lps, counts, fin_map) awaiting detokenisation
         # callable(List[RequestOutput]) taking overlap-window outputs immediately (a server
@@ -288,6 +289,12 @@ class LLMEngine:
             raise ValueError(f"prompt token ids must be in [0, {V}), got [{min(prompt_ids)}, {max(prompt_ids)}]")
         if not params.plain:
             self._check_processors(params)
+        if params.top_logprobs:
+            from ..ops import TOPLP_MAX
+            if isinstance(params.top_logprobs, bool) or not isinstance(params.top_logprobs, int) \
+                    or not 0 <= params.top_logprobs <= TOPLP_MAX:
+                raise UnsupportedSampling("top_logprobs", f"must be an integer between 0 and {TOPLP_MAX}")
+            params.logprobs = True
         max_tokens = params.max_tokens
         if kind != RequestType.Embeddings:
             max_tokens = min(max_tokens, self.max_model_len - len(prompt_ids))
@@ -378,6 +385,7 @@ class LLMEngine:
             self.slot_req[s] = r
             self.slot_ngen[s] = len(r.output_ids) if r is not None else 0
             self.slot_pen[:, s] = (1.0, 0.0, 0.0, -np.inf)
+            self.slot_topn[s] = 0 if r is None else r.params.top_logprobs
             self.slot_track[s], self.slot_blen[s], self.slot_proc[s] = -1, 0, False
             self._resets.pop(s, None)
             if r is None:
@@ -444,6 +452,8 @@ class LLMEngine:
                 x = (x * np.uint64(0xBF58476D1CE4E5B9)) & np.uint64(_MASK63)
             seeds = x.view(np.int64)
         samp = SamplingRows(temps, self.slot_topp[slots], self.slot_topk[slots], seeds)
+        if self.slot_topn[slots].any():
+            samp.topn = self.slot_topn[slots]
         if self.slot_proc[slots].any():
             samp.slots, samp.bias_lens, samp.pens = self.slot_track[slots], self.slot_blen[slots], self.slot_pen[:, slots]
             if self._resets:
@@ -565,6 +575,7 @@ class LLMEngine:
         t = self._tick("emit_overlapped", t)
         toks, lps, hidden = self.runner.wait(handle)
         plan["_t_tokens"] = time.monotonic()
+        plan["_top"] = self.runner.top_result
         t = self._tick("wait_gpu", t)
         n_sample = int(plan["num_sample"])
         counts = np.ones(n_sample, np.int32)
@@ -618,6 +629,7 @@ class LLMEngine:
             t = self._tick("emit_overlapped", t)
             toks, lps, hidden = self.runner.wait(handle)
             plan["_t_tokens"] = time.monotonic()
+            plan["_top"] = self.runner.top_result
             t = self._tick("wait_gpu", t)
         if counts is None:
             counts = np.ones(int(plan["num_sample"]), np.int32)
@@ -742,6 +754,7 @@ class LLMEngine:
         now = time.monotonic()
         sidx = plan["sample_seq_index"]
         t_tok = plan.get("_t_tokens", now)
+        tops = plan.get("_top")  # per sampled token, beside toks / lps: [(id, lp)] of a row that asked
         k = 0
         for j in range(n_sample):
             c = int(counts[j])
@@ -755,6 +768,10 @@ class LLMEngine:
             take = c if f is None else max(1, min(c, f[3] - len(req.output_ids)))
             new = [int(t) for t in toks[k:k + take]]
             new_lps = [float(x) for x in lps[k:k + take]] if (lps is not None and req.params.logprobs) else None
+            new_top = None
+            if tops is not None and req.params.top_logprobs > 0:
+                kk = req.params.top_logprobs
+                new_top = [[(int(i), float(l)) for i, l in (row or [])[:kk] if i >= 0] for row in tops[k:k + take]]
             k += c
             if req.first_token_time is None:
                 req.first_token_time = now
@@ -772,7 +789,7 @@ class LLMEngine:
             out = RequestOutput(req.request_id, new, text, reason is not None,
                                 FINISH_NAMES.get(reason) if reason else None,
                                 prompt_tokens=len(req.prompt_ids), completion_tokens=len(req.output_ids),
-                                logprobs=new_lps, t_tokens=t_tok)
+                                logprobs=new_lps, t_tokens=t_tok, top_logprobs=new_top)
             if reason is not None:
                 out.cached_tokens = req.cached_tokens
                 self._finish(req, reason)

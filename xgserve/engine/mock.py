@@ -138,9 +138,17 @@ class MockEngine:
                 if reason is not None and not r.detok.stopped:
                     text += r.detok.flush()
                 self.stats_counters["generation_tokens"] += 1
+                lps = top = None
+                k = int(r.params.top_logprobs or 0)
+                if k > 0:
+                    # deterministic lists: the emitted token first, then fixed ids (3, 4, ...,
+                    # skipping the token) with descending log-probabilities
+                    lps = [-0.25]
+                    alt = [i for i in range(3, 3 + k + 1) if i != tok][:k - 1]
+                    top = [[(tok, -0.25)] + [(i, -1.0 - 0.5 * j) for j, i in enumerate(alt)]]
                 outs.append(RequestOutput(rid, [tok], text, reason is not None, reason,
                                           prompt_tokens=len(r.prompt_ids), completion_tokens=len(r.output_ids),
-                                          t_tokens=time.monotonic()))
+                                          logprobs=lps, t_tokens=time.monotonic(), top_logprobs=top))
                 if reason is not None:
                     self._drop(rid)
         return outs

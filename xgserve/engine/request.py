@@ -11,7 +11,7 @@ from __future__ import annotations
 import enum
 import time
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 
 class RequestType(str, enum.Enum):
@@ -32,6 +32,7 @@ class SamplingParams:
     min_tokens: int = 0
     seed: Optional[int] = None
     logprobs: bool = False
+    top_logprobs: int = 0  # alternatives per token (0..20); > 0 implies logprobs
     # logit processors (ops/sampling.py process_logits), all neutral by default
     min_p: float = 0.0
     repetition_penalty: float = 1.0
@@ -88,6 +89,9 @@ class RequestOutput:
     # (encoded by the replica process that produced it, so the HTTP process only
     # writes bytes: server/replica.py encode_sse_chunk); None: encode on the server
     sse: Optional[bytes] = None
+    # per new token, the `top_logprobs` most likely (token id, logprob) pairs, best first
+    # (SamplingParams.top_logprobs > 0; entries the row did not have are left out)
+    top_logprobs: Optional[List[List[Tuple[int, float]]]] = None
 
 
 @dataclass

@@ -62,6 +62,9 @@ class SamplingRows:
     # slots bound since the last processed step, reset ahead of this one on every rank:
     # [(slot, unique ids, cells, bias ids, bias values)]
     resets: Optional[list] = None
+    # top-N alternatives (ops.top_logprobs): int32 entries asked per row, None: no row asked
+    # and the step enqueues nothing for them
+    topn: Optional[np.ndarray] = None
 
     @property
     def all_greedy(self) -> bool:
@@ -156,6 +159,11 @@ class ModelRunner:
         self.h_toks = [_pinned(nt, torch.int32) for _ in range(2)]
         self.h_lps = [_pinned(nt, torch.float32) for _ in range(2)]
         self.out_idx = 0
+        # top-N alternatives: nothing of this exists until a step asks (_top_init)
+        self.t_out = None             # static device buffer: ids [n, K] | logprobs [n, K] of the asking rows
+        self.top_result = None        # per sampled row of the step wait() last returned: [(id, lp)] or None
+        self._top_last = None
+        self._top_pending: Dict[int, tuple] = {}
         self._es_pin = [None, None]   # eager-step sampling rows: pinned stagings + events
         self._es_ev = [None, None]
         self._es_idx = 0
@@ -290,6 +298,7 @@ class ModelRunner:
             self.g_out_lp[:bs].copy_(lp)
         if proc and self.p_state is not None:
             ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, bs)
+        return logits  # what the sampler read: kept by the graph for an eager top_logprobs after a replay
 
     def _mixed_body(self, nb: int, greedy: bool, proc: bool = False):
         """nb decode rows (padded) + one prompt chunk of up to C rows (padded) -> the
@@ -324,6 +333,7 @@ class ModelRunner:
             self.g_out_lp[:nb + 1].copy_(lp)
         if proc and self.p_state is not None:
             ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, nb + 1)
+        return logits
 
     # ------------------------------------------------------------------ logit processors
     def _proc_init(self) -> None:
@@ -495,7 +505,10 @@ class ModelRunner:
         for key, fn in bodies:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode=error_mode):
-                fn()
+                kept = fn()
+            # the body's logits rows stay referenced, so no later capture of the pool reuses
+            # their storage: a replay leaves them readable until the next replay
+            g.xgs_logits = kept
             out[key] = g
         torch.cuda.synchronize()
         return out
@@ -568,6 +581,13 @@ class ModelRunner:
         while the GPU runs. `src` (asynchronous scheduling): per decode row, the
         row of the previous GRAPH step whose sampled token is this row's input
         (-1: the plan's own id)."""
+        self._top_last = None
+        h = self._launch(plan, samp, src)
+        if self._top_last is not None:
+            self._top_pending[id(h)] = (h, self._top_last)  # the handle is held: its id stays its own
+        return h
+
+    def _launch(self, plan: dict, samp: Optional[SamplingRows], src: Optional[np.ndarray]):
         T = int(plan["num_tokens"])
         Nd = int(plan["num_decodes"])
         ns = int(plan["num_seqs"])
@@ -636,7 +656,71 @@ class ModelRunner:
                 ev.synchronize()
                 return
 
+    # ------------------------------------------------------------------ top-N alternatives
+    def _top_init(self) -> None:
+        if self.t_out is not None:
+            return
+        nt, K = max(self.max_tokens, self.max_num_seqs, self.g_OB), ops.TOPLP_MAX
+        self._t_rows = nt
+        self.t_out = torch.zeros(2 * nt * K, dtype=torch.int32, device=self.device)
+        # per output buffer (out_idx): results, and the inputs [asking rows | temperatures]
+        self.h_tops = [_pinned(2 * nt * K, torch.int32) for _ in range(2)]
+        self.h_tins = [_pinned(2 * nt, torch.int32) for _ in range(2)]
+
+    def _top_launch(self, logits: torch.Tensor, samp: SamplingRows) -> None:
+        """ops.top_logprobs over the rows of `logits` (what this step's sampler read, in
+        sample order) that asked, into the static buffer, and its D2H into the pinned
+        buffer of the step's output set -- queued in front of the step's token copy, so the
+        event wait() waits on covers it and the pinned sets are fenced as h_gout is."""
+        S = len(samp.temps)
+        ask = np.nonzero(samp.topn[:S] > 0)[0].astype(np.int32)
+        na = int(ask.shape[0])
+        if na == 0 or not self.is_driver:
+            return
+        K = int(min(ops.TOPLP_MAX, samp.topn.max()))
+        if not self.is_cuda:
+            rows = torch.from_numpy(ask)
+            ids, lps = ops.top_logprobs(logits[:S], torch.from_numpy(np.ascontiguousarray(samp.temps, np.float32)), K,
+                                        rows)
+            self._top_last = (ask, K, S, ids.numpy(), lps.numpy())
+            return
+        self._top_init()
+        assert S <= self._t_rows and logits.shape[0] >= S
+        i = self.out_idx
+        hin = self.h_tins[i]
+        a = hin.numpy()
+        a[:na] = ask
+        a[na:na + S].view(np.float32)[:] = samp.temps
+        d = hin[:na + S].to(self.device, non_blocking=True)
+        o = self.t_out
+        ops.top_logprobs(logits[:S], d[na:].view(torch.float32), K, d[:na], o[:na * K],
+                         o[na * K:2 * na * K].view(torch.float32))
+        self.h_tops[i][:2 * na * K].copy_(o[:2 * na * K], non_blocking=True)
+        self._top_last = (ask, K, S, i)
+
+    def _top_collect(self, handle):
+        p = self._top_pending.pop(id(handle), None)
+        if p is None:
+            return None
+        ask, K, S = p[1][:3]
+        na = ask.shape[0]
+        if len(p[1]) == 4:
+            h = self.h_tops[p[1][3]].numpy()
+            ids = h[:na * K].reshape(na, K).copy()
+            lps = h[na * K:2 * na * K].view(np.float32).reshape(na, K).copy()
+        else:
+            ids, lps = p[1][3], p[1][4]
+        top = [None] * S
+        for j, r in enumerate(ask.tolist()):
+            top[r] = list(zip(ids[j].tolist(), lps[j].tolist()))
+        return top
+
     def wait(self, handle):
+        res = self._wait(handle)
+        self.top_result = self._top_collect(handle) if self._top_pending else None
+        return res
+
+    def _wait(self, handle):
         n, hidden, ready, out = handle[:4]
         if ready is not None:
             return ready
@@ -692,6 +776,8 @@ class ModelRunner:
         ev.record()
         self.g_stage_events[si] = ev
         graph.replay()
+        if samp is not None and samp.topn is not None:
+            self._top_launch(graph.xgs_logits, samp)
         self._log_samples(n)
         if not self.is_driver:
             # no D2H to wait on; wait() still drains before the pinned inputs get rewritten
@@ -750,6 +836,8 @@ class ModelRunner:
         ev.record()
         self.g_stage_events[si] = ev
         graph.replay()
+        if samp is not None and samp.topn is not None:
+            self._top_launch(graph.xgs_logits, samp)
         self.mixed_replays += 1
         self._log_samples(n)
         if not self.is_driver:
@@ -894,6 +982,8 @@ class ModelRunner:
             tok, lp = ops.sample_tokens(out, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
         if self.p_state is not None:
             ops.logit_state_update(self.p_state, d_pi[0], tok, n)
+        if samp.topn is not None:
+            self._top_launch(out, samp)
         return tok, lp
 
     def _sample(self, logits: torch.Tensor, samp: Optional[SamplingRows]):
@@ -932,6 +1022,8 @@ class ModelRunner:
             seeds = torch.from_numpy(samp.seeds.astype(np.int64))
             gen = torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
             tok, lp = ops.sample_tokens(logits, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
+        if samp is not None and samp.topn is not None:
+            self._top_launch(logits, samp)
         return tok, lp
 
     def _log_samples(self, n: int) -> None:

@@ -254,10 +254,14 @@ class SpeculativeDecoder:
         if samp is not None:
             rsamp = SamplingRows(np.repeat(samp.temps, nrows), np.repeat(samp.top_ps, nrows),
                                  np.repeat(samp.top_ks, nrows), np.repeat(samp.seeds, nrows))
+            if samp.topn is not None:
+                rsamp.topn = np.repeat(samp.topn, nrows)
         toks, lps, hidden = self.engine.runner.execute(plan, rsamp)
         if toks is None:
             return None, None, hidden, None
         out_t, out_l, counts = [], [], []
+        tops = self.engine.runner.top_result  # per verify row; sliced to the accepted positions as lps
+        out_top = [] if tops is not None else None
         k = 0
         qsl, ids, seq_ids = plan["query_start_loc"], plan["input_ids"], plan["seq_ids"]
         for j, s in enumerate(sidx.tolist()):
@@ -266,6 +270,8 @@ class SpeculativeDecoder:
                 out_t.append(int(toks[k]))
                 out_l.append(float(lps[k]))
                 counts.append(1)
+                if tops is not None:
+                    out_top.append(tops[k])
                 k += 1
                 continue
             draft = ids[int(qsl[s]) + 1:int(qsl[s]) + n_r]
@@ -276,8 +282,11 @@ class SpeculativeDecoder:
             out_t.extend(int(x) for x in t[:n + 1])  # accepted drafts == target tokens, + the bonus token
             out_l.extend(float(x) for x in lps[k:k + n + 1])
             counts.append(n + 1)
+            if tops is not None:
+                out_top.extend(tops[k:k + n + 1])
             k += n_r
             self._account(int(seq_ids[s]), n_r - 1, n)
+        plan["_top"] = out_top
         return (np.asarray(out_t, np.int32), np.asarray(out_l, np.float32), hidden, np.asarray(counts, np.int32))
 
     def _account(self, sid: int, proposed: int, accepted: int) -> None:

@@ -109,6 +109,93 @@ def sample_tokens(logits: torch.Tensor, temps: torch.Tensor, top_ps: Optional[to
     return tok, lp
 
 
+# ---------------------------------------------------------------------------
+# Top-K alternatives (csrc/kernels/top_logprobs.hip)
+# ---------------------------------------------------------------------------
+TOPLP_MAX = 20
+_TOPLP_WS = {}
+
+
+def _toplp_ws(device, n: int):
+    """Split-row scratch of top_logprobs: per-slice winners and zeroed per-row tickets
+    (re-armed by every launch), grown on demand; earlier ones stay alive for captured graphs."""
+    wss = _TOPLP_WS.setdefault((device.type, device.index), [])
+    if not wss or wss[-1][1].numel() < n:
+        m = max(n, 64)
+        wss.append((torch.empty(m * kernels().top_logprobs_ws_words(), dtype=torch.int64, device=device),
+                    torch.zeros(m, dtype=torch.int32, device=device)))
+    return wss[-1]
+
+
+def top_logprobs_ref(logits: torch.Tensor, temps: torch.Tensor, k: int, rows: Optional[torch.Tensor] = None):
+    """numpy: y = fp32(x * fp32(1 / T)) (x on a greedy row), lp = y - logZ over the whole
+    row (float64), ordered by y descending, then token id; -inf logits are not listed
+    (id -1, lp -inf in the slots left over)."""
+    import numpy as np
+    lf = logits.detach().float().cpu().numpy()
+    tn = temps.detach().float().cpu().numpy()
+    ridx = np.arange(lf.shape[0]) if rows is None else rows.detach().cpu().numpy().astype(np.int64)
+    n = len(ridx)
+    ids = np.full((n, k), -1, np.int32)
+    lps = np.full((n, k), -np.inf, np.float32)
+    with np.errstate(all="ignore"):
+        for o, r in enumerate(ridx):
+            t = np.float32(tn[r])
+            y = (lf[r] * (np.float32(1) / t)).astype(np.float32) if t > 0 else lf[r]
+            fin = y > -np.inf
+            if not fin.any():
+                continue
+            y64 = y.astype(np.float64)
+            m = y64[fin].max()
+            logz = m + np.log(np.exp(y64[fin] - m).sum())
+            order = np.argsort(-y, kind="stable")[:k]
+            order = order[fin[order]]
+            ids[o, :len(order)] = order
+            lps[o, :len(order)] = (y64[order] - logz).astype(np.float32)
+    return torch.from_numpy(ids), torch.from_numpy(lps)
+
+
+def top_logprobs(logits: torch.Tensor, temps: torch.Tensor, k: int, rows: Optional[torch.Tensor] = None,
+                 out_ids: Optional[torch.Tensor] = None, out_lps: Optional[torch.Tensor] = None):
+    """The k (1..TOPLP_MAX) most likely tokens of the asked rows of a [R, V] logits matrix
+    and their log-probabilities under the temperature-scaled distribution of the whole row
+    (the one the samplers' logprob refers to; temps <= 0: the raw logits). rows: int32
+    indices of the logits rows that asked (None: all, in order); temps: fp32 indexed by
+    logits row. Returns (ids int32 [n, k], lps fp32 [n, k]), best first, equal values to
+    the lower id; id -1 / lp -inf past the last finite entry."""
+    if not 1 <= k <= TOPLP_MAX:
+        raise ValueError(f"top_logprobs: k must be in [1, {TOPLP_MAX}]")
+    R, V = logits.shape
+    n = R if rows is None else rows.numel()
+    if not use_native(logits):
+        ids, lps = top_logprobs_ref(logits, temps, k, rows)
+        if out_ids is not None:
+            out_ids[:n, :k].copy_(ids)
+            out_lps[:n, :k].copy_(lps)
+        return ids, lps
+    assert logits.stride(1) == 1 and logits.dtype in (torch.bfloat16, torch.float32)
+    assert temps.dtype == torch.float32 and temps.is_contiguous() and temps.numel() >= R
+    assert rows is None or (rows.dtype == torch.int32 and rows.is_contiguous())
+    if out_ids is None:
+        out_ids = torch.empty(n, k, dtype=torch.int32, device=logits.device)
+        out_lps = torch.empty(n, k, dtype=torch.float32, device=logits.device)
+    else:  # the first n * k elements of the caller's buffers, as [n, k]
+        assert out_ids.dtype == torch.int32 and out_lps.dtype == torch.float32
+        assert out_ids.is_contiguous() and out_lps.is_contiguous() and min(out_ids.numel(), out_lps.numel()) >= n * k
+        out_ids = out_ids.view(-1)[:n * k].view(n, k)
+        out_lps = out_lps.view(-1)[:n * k].view(n, k)
+    if n == 0:
+        return out_ids, out_lps
+    ws = tk = wrows = 0
+    if V >= ARGMAX_SPLIT_MIN_V:
+        w, t = _toplp_ws(logits.device, n)
+        ws, tk, wrows = w.data_ptr(), t.data_ptr(), t.numel()
+    kernels().top_logprobs(logits.data_ptr(), 1 if logits.dtype == torch.float32 else 0, logits.stride(0), R, V,
+                           ptr(rows), n, temps.data_ptr(), k, out_ids.data_ptr(), out_lps.data_ptr(), stream_ptr(),
+                           ws, tk, wrows)
+    return out_ids, out_lps
+
+
 # Split-row sampler (csrc/kernels/sampling.hip "sample v2": several workgroups per row,
 # histogram thresholds instead of a 24-pass bisection); False selects the
 # one-workgroup-per-row kernel (the tests' cross-check; A/B in profiles/r2_sampling.md).

@@ -32,7 +32,7 @@ from ..core.errors import ApiError, ApiInternal, ApiValidationError, ConfigError
 from ..core.types import Priority
 from ..core.wire import (ChatChoice, ChatMessage, ChatRequest, ChatResponse, EmbeddingData, EmbeddingsRequest,
                          EmbeddingsResponse, FinishReason, GenerateChoice, GenerateRequest, GenerateResponse, Role,
-                         PROCESSOR_FIELDS, TokenEvent, Usage)
+                         PROCESSOR_FIELDS, TokenEvent, Usage, top_logprobs_field)
 from ..engine.request import RequestType, SamplingParams
 from ..obs import trace
 from .orchestrator import InferenceServer, ServerRequest, sse_chunk
@@ -102,12 +102,55 @@ def _params(max_tokens, temperature, top_p, stop, seed=None, ignore_eos=False, l
         sp.min_p, sp.repetition_penalty = float(req.min_p), float(req.repetition_penalty)
         sp.presence_penalty, sp.frequency_penalty = float(req.presence_penalty), float(req.frequency_penalty)
         sp.logit_bias = dict(req.logit_bias)
+        sp.top_logprobs = int(req.top_logprobs)
+        sp.logprobs = bool(sp.logprobs or req.logprobs or sp.top_logprobs > 0)
     return sp
+
+
+def _tok_text(srv, tid: int) -> str:
+    return srv.tokenizer.decode([int(tid)])
+
+
+def _lp_native(srv, ids, lps, tops) -> dict:
+    """`choices[0].logprobs` of /generate and /chat."""
+    d = {"tokens": [_tok_text(srv, t) for t in ids], "token_ids": [int(t) for t in ids],
+         "token_logprobs": [float(x) for x in lps],
+         "top_logprobs": [[{"token": _tok_text(srv, i), "token_id": int(i), "logprob": float(lp)} for i, lp in t]
+                          for t in tops]}
+    return d
+
+
+def _lp_completions(srv, ids, lps, tops, offset: int = 0) -> dict:
+    """OpenAI text-completion logprobs; text_offset counts the decoded single tokens from `offset`."""
+    toks = [_tok_text(srv, t) for t in ids]
+    offs = []
+    for t in toks:
+        offs.append(offset)
+        offset += len(t)
+    return {"tokens": toks, "token_logprobs": [float(x) for x in lps],
+            "top_logprobs": [{_tok_text(srv, i): float(lp) for i, lp in t} for t in tops], "text_offset": offs}
+
+
+def _lp_chat(srv, ids, lps, tops) -> dict:
+    """OpenAI chat-completion logprobs."""
+    def ent(i, lp):
+        s = _tok_text(srv, i)
+        return {"token": s, "logprob": float(lp), "bytes": list(s.encode("utf-8"))}
+    return {"content": [dict(ent(t, lp), top_logprobs=[ent(i, l) for i, l in top])
+                        for t, lp, top in zip(ids, lps, tops)]}
+
+
+def _result_lp(r):
+    """(ids, logprobs, alternatives per token) of a finished request; alternatives are [] where none were asked."""
+    ids, lps = list(r.lp_token_ids), list(r.logprobs)
+    tops = list(r.top_logprobs) if r.top_logprobs else [[] for _ in ids]
+    return ids, lps, tops
 
 
 def _validate_processors(srv: InferenceServer, req) -> None:
     """Ranges of the sampling extensions (400, `Invalid parameter '<field>': <reason>`);
     a server that decodes speculatively accepts plain requests only."""
+    InferenceServer._raise_validation(srv.validator.check_top_logprobs(int(req.top_logprobs)))
     res = srv.validator.check_processors(req.min_p, req.repetition_penalty, req.presence_penalty,
                                          req.frequency_penalty, list(req.logit_bias.keys()),
                                          list(req.logit_bias.values()),
@@ -229,7 +272,10 @@ async def handle_generate(request: web.Request) -> web.StreamResponse:
         return await _sse(request, srv, sreq)
     r = await _await_result(request, srv, sreq)
     resp = GenerateResponse.build(srv.model_name, [GenerateChoice(r.text, 0, r.finish_reason)], r.usage(), rid=r.id)
-    return _json(resp.to_dict())
+    out = resp.to_dict()
+    if sp.logprobs:
+        out["choices"][0]["logprobs"] = _lp_native(srv, *_result_lp(r))
+    return _json(out)
 
 
 async def handle_chat(request: web.Request) -> web.StreamResponse:
@@ -239,14 +285,18 @@ async def handle_chat(request: web.Request) -> web.StreamResponse:
         srv.validate_chat([m.content for m in req.messages], req.max_tokens, req.temperature, req.top_p)
         _validate_processors(srv, req)
     ids = srv.encode(srv.tokenizer.apply_chat_template(req.messages))
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req=req)
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req.logprobs,
+                 req=req)
     sreq = await srv.aadmit(RequestType.Chat, ids, sp, Priority.Normal, stream=req.stream, sse_native=req.stream)
     if req.stream:
         return await _sse(request, srv, sreq)
     r = await _await_result(request, srv, sreq)
     resp = ChatResponse.build(srv.model_name, [ChatChoice(0, ChatMessage(Role.Assistant, r.text), r.finish_reason)],
                               r.usage(), rid=r.id)
-    return _json(resp.to_dict())
+    out = resp.to_dict()
+    if sp.logprobs:
+        out["choices"][0]["logprobs"] = _lp_native(srv, *_result_lp(r))
+    return _json(out)
 
 
 async def _embed(srv: InferenceServer, inputs, request) -> tuple:
@@ -375,19 +425,29 @@ async def handle_v1_completions(request: web.Request) -> web.StreamResponse:
     if body["prompt"] is None:
         body.pop("prompt")
     body["stop_sequences"] = _oa_stop(d)
+    if d.get("logprobs") is not None:  # OpenAI: an integer, the number of alternatives (0: the token's own only)
+        body["top_logprobs"] = top_logprobs_field(d, "logprobs")
+        body["logprobs"] = True
     req = GenerateRequest.parse(body)
     srv.validate_generate(req.prompt, req.max_tokens, req.temperature, req.top_p)
     _validate_processors(srv, req)
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req=req)
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, logprobs=req.logprobs,
+                 req=req)
     sreq = await srv.aadmit(RequestType.Generate, srv.encode(req.prompt), sp,
                      req.priority if req.priority is not None else Priority.Normal, stream=req.stream)
     created = int(time.time())
     if req.stream:
+        offset = [0]
+
         def fmt(ev: TokenEvent):
             if ev.type == "error":
                 return ev.sse()
             ch = {"text": ev.token if ev.type == "token" else "", "index": 0,
                   "finish_reason": _oa_finish(ev) if ev.type == "done" else None}
+            if ev.type == "token" and ev.detail:
+                ids, lps, tops = zip(*ev.detail)
+                ch["logprobs"] = _lp_completions(srv, ids, lps, [t or [] for t in tops], offset[0])
+                offset[0] += sum(len(t) for t in ch["logprobs"]["tokens"])
             return b"data: " + json.dumps({"id": sreq.id, "object": "text_completion", "created": created,
                                            "model": srv.model_name, "choices": [ch]}).encode() + b"\n\n"
         return await _sse(request, srv, sreq, fmt)
@@ -396,6 +456,8 @@ async def handle_v1_completions(request: web.Request) -> web.StreamResponse:
                                  rid=r.id).to_dict()
     out["choices"][0]["finish_reason"] = "stop" if r.finish_reason == FinishReason.StopSequence else \
         r.finish_reason.value
+    if sp.logprobs:
+        out["choices"][0]["logprobs"] = _lp_completions(srv, *_result_lp(r))
     return _json(out)
 
 
@@ -405,14 +467,22 @@ async def handle_v1_chat(request: web.Request) -> web.StreamResponse:
     if not isinstance(d, dict):
         raise ValidationError.invalid_json("invalid type: expected a JSON object")
     body = {k: v for k, v in d.items()
-            if k in ("messages", "max_tokens", "temperature", "top_p", "stream", "seed") + PROCESSOR_FIELDS}
+            if k in ("messages", "max_tokens", "temperature", "top_p", "stream", "seed", "top_logprobs")
+            + PROCESSOR_FIELDS}
     if "max_completion_tokens" in d and "max_tokens" not in body:
         body["max_tokens"] = d["max_completion_tokens"]
     body["stop_sequences"] = _oa_stop(d)
+    if d.get("logprobs") is not None:
+        if not isinstance(d["logprobs"], bool):
+            raise ValidationError.invalid_parameter("logprobs", "must be a boolean")
+        body["logprobs"] = d["logprobs"]
     req = ChatRequest.parse(body)
     srv.validate_chat([m.content for m in req.messages], req.max_tokens, req.temperature, req.top_p)
     _validate_processors(srv, req)
-    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req=req)
+    if req.top_logprobs > 0 and not req.logprobs:
+        raise ValidationError.invalid_parameter("top_logprobs", "requires logprobs to be true")
+    sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, logprobs=req.logprobs,
+                 req=req)
     sreq = await srv.aadmit(RequestType.Chat, srv.encode(srv.tokenizer.apply_chat_template(req.messages)), sp,
                      Priority.Normal, stream=req.stream)
     created = int(time.time())
@@ -422,6 +492,9 @@ async def handle_v1_chat(request: web.Request) -> web.StreamResponse:
                 return ev.sse()
             delta = {"content": ev.token} if ev.type == "token" else {}
             ch = {"index": 0, "delta": delta, "finish_reason": _oa_finish(ev) if ev.type == "done" else None}
+            if ev.type == "token" and ev.detail:
+                ids, lps, tops = zip(*ev.detail)
+                ch["logprobs"] = _lp_chat(srv, ids, lps, [t or [] for t in tops])
             return b"data: " + json.dumps({"id": sreq.id, "object": "chat.completion.chunk", "created": created,
                                            "model": srv.model_name, "choices": [ch]}).encode() + b"\n\n"
         return await _sse(request, srv, sreq, fmt)
@@ -430,6 +503,8 @@ async def handle_v1_chat(request: web.Request) -> web.StreamResponse:
                              r.usage(), rid=r.id).to_dict()
     out["choices"][0]["finish_reason"] = "stop" if r.finish_reason == FinishReason.StopSequence else \
         r.finish_reason.value
+    if sp.logprobs:
+        out["choices"][0]["logprobs"] = _lp_chat(srv, *_result_lp(r))
     return _json(out)
 
 

@@ -272,7 +272,8 @@ class FrontendHub:
         self.send(wid, ("res", sreq.id, True, {
             "id": r.id, "text": r.text, "finish_reason": r.finish_reason.value if r.finish_reason else "stop",
             "prompt_tokens": r.prompt_tokens, "completion_tokens": r.completion_tokens,
-            "embedding": r.embedding, "logprobs": list(r.logprobs)}))
+            "embedding": r.embedding, "logprobs": list(r.logprobs), "lp_token_ids": list(r.lp_token_ids),
+            "top_logprobs": [[list(e) for e in t] for t in r.top_logprobs]}))
 
     def _on_msgs(self, wid: int, msgs: List[tuple]) -> None:
         srv = self.srv
@@ -407,6 +408,8 @@ class _Result:
         self.completion_tokens = d["completion_tokens"]
         self.embedding = d["embedding"]
         self.logprobs = d["logprobs"]
+        self.lp_token_ids = d.get("lp_token_ids") or []
+        self.top_logprobs = d.get("top_logprobs") or []
 
     def usage(self) -> Usage:
         return Usage.new(self.prompt_tokens, self.completion_tokens)

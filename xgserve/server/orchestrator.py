@@ -38,7 +38,7 @@ from ..router import Router
 from .batcher import RequestBatcher
 from .config import ServerConfig, apply_hot_reload
 from .degradation import DegradationLevel
-from .replica import InProcessReplica, ProcessReplica, Replica, engine_spec
+from .replica import InProcessReplica, ProcessReplica, Replica, engine_spec, top_logprob_dicts
 from .streamer import StreamSender, TokenStreamer
 
 log = logging.getLogger("xgserve.server")
@@ -106,14 +106,16 @@ class RemoteWire:
 def ev_to_tuple(ev: TokenEvent) -> tuple:
     u = ev.usage
     return (ev.type, ev.token, ev.index, ev.logprob, ev.finish_reason.value if ev.finish_reason else None,
-            (u.prompt_tokens, u.completion_tokens) if u is not None else None, ev.message, ev.code)
+            (u.prompt_tokens, u.completion_tokens) if u is not None else None, ev.message, ev.code,
+            ev.top_logprobs, ev.detail)
 
 
 def ev_from_tuple(t: tuple) -> TokenEvent:
-    typ, token, index, logprob, fr, u, message, code = t
+    typ, token, index, logprob, fr, u, message, code, top, detail = t
     return TokenEvent(typ, token=token, index=index, logprob=logprob,
                       finish_reason=FinishReason(fr) if fr is not None else None,
-                      usage=Usage.new(*u) if u is not None else None, message=message, code=code)
+                      usage=Usage.new(*u) if u is not None else None, message=message, code=code,
+                      top_logprobs=top, detail=detail)
 
 
 class ServerRequest:
@@ -139,6 +141,11 @@ class ServerRequest:
         self.high = False
         self.text_parts: List[str] = []
         self.logprobs: List[float] = []
+        # with logprobs: the token ids the logprobs belong to, and (top_logprobs > 0) each
+        # token's alternatives [(id, logprob)]
+        self.lp_token_ids: List[int] = []
+        self.top_logprobs: List[list] = []
+        self.pending_detail: list = []  # OpenAI-alias streams: tokens not yet attached to an event
         self.completion_tokens = 0
         self.cached_tokens = 0
         self.embedding: Optional[List[float]] = None
@@ -617,12 +624,20 @@ class InferenceServer:
                 sreq.completion_tokens = o.completion_tokens or (sreq.completion_tokens + len(o.new_token_ids))
                 if o.logprobs:
                     sreq.logprobs.extend(o.logprobs)
+                    if sreq.sender is None:
+                        sreq.lp_token_ids.extend(o.new_token_ids)
+                        if o.top_logprobs:
+                            sreq.top_logprobs.extend(o.top_logprobs)
+                    elif not sreq.sse_native:
+                        sreq.pending_detail.extend(zip(o.new_token_ids, o.logprobs,
+                                                       o.top_logprobs or [None] * len(o.logprobs)))
                 if sreq.sender is not None:
                     if o.new_text:
                         w = sreq.wire
                         if w is not None:  # direct: write the (pre-encoded) chunk to the socket now
                             chunk = o.sse if o.sse is not None else sse_chunk(TokenEvent.tok(
-                                o.new_text, sreq.completion_tokens - 1, o.logprobs[-1] if o.logprobs else None))
+                                o.new_text, sreq.completion_tokens - 1, o.logprobs[-1] if o.logprobs else None,
+                                self._top_dicts(o)))
                             if w.__class__ is RemoteWire:
                                 w.send(chunk, o.t_tokens)  # the front end writes it and times the delivery
                             elif self._wire_ok(sreq, w):
@@ -631,7 +646,9 @@ class InferenceServer:
                                 t_wire = o.t_tokens
                         else:
                             ev = TokenEvent.tok(o.new_text, sreq.completion_tokens - 1,
-                                                o.logprobs[-1] if o.logprobs else None)
+                                                o.logprobs[-1] if o.logprobs else None, self._top_dicts(o))
+                            if sreq.pending_detail:
+                                ev.detail, sreq.pending_detail = sreq.pending_detail, []
                             ev.t_tokens = o.t_tokens  # not serialised: delivery-delay measurement (Req 5.1)
                             sreq.sender.send(ev)
                 else:
@@ -653,6 +670,12 @@ class InferenceServer:
             if o.finished:
                 if o.finish_reason == "abort":
                     continue  # aborted by us (cancel/timeout) -- already answered
+                if sreq.pending_detail and sreq.sender is not None:
+                    # tokens whose text never came out (held back by the detokenizer): their
+                    # log-probabilities ride an event without text
+                    ev = TokenEvent.tok("", max(0, sreq.completion_tokens - 1))
+                    ev.detail, sreq.pending_detail = sreq.pending_detail, []
+                    sreq.sender.send(ev)
                 sreq.cached_tokens = o.cached_tokens
                 sreq.finish_reason = _FINISH.get(o.finish_reason or "stop", FinishReason.Stop)
                 self._finalize(sreq)
@@ -663,6 +686,12 @@ class InferenceServer:
             self.metrics.record_itl_many(itl)
         if n_wire and t_wire:
             self.metrics.record_delivery(time.monotonic() - t_wire, n_wire)
+
+    def _top_dicts(self, o: RequestOutput):
+        """The wire form of an output's last token's alternatives (None: not asked)."""
+        if not o.top_logprobs:
+            return None
+        return top_logprob_dicts(self.tokenizer, o.top_logprobs[-1])
 
     def _finalize(self, sreq: ServerRequest) -> None:
         if sreq.finished:

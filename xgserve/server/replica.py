@@ -101,13 +101,21 @@ def _is_oom(e: BaseException) -> bool:
 # ---------------------------------------------------------------------------
 # the worker main loop
 # ---------------------------------------------------------------------------
-def encode_sse_chunk(text: str, index: int, logprob: Optional[float] = None) -> bytes:
+def top_logprob_dicts(tokenizer, top) -> list:
+    """[(token id, logprob)] -> the wire form [{"token", "token_id", "logprob"}]; `token` is
+    the tokenizer's decoding of that single id."""
+    return [{"token": tokenizer.decode([i]), "token_id": i, "logprob": lp} for i, lp in top]
+
+
+def encode_sse_chunk(text: str, index: int, logprob: Optional[float] = None, top: Optional[list] = None) -> bytes:
     """One native SSE token event (byte-identical to core.wire.TokenEvent.tok(...).sse())
-    framed as an HTTP/1.1 chunk, ready for the client socket."""
+    framed as an HTTP/1.1 chunk, ready for the client socket. top: top_logprob_dicts(...)."""
     body = b'data: {"type":"token","token":' + json.dumps(text).encode()
     body += b',"index":' + str(index).encode()
     if logprob is not None:
         body += b',"logprob":' + json.dumps(logprob).encode()
+    if top is not None:
+        body += b',"top_logprobs":' + json.dumps(top, separators=(",", ":")).encode()
     body += b"}\n\n"
     return b"%x\r\n%s\r\n" % (len(body), body)
 
@@ -140,7 +148,9 @@ class EngineLoop:
             if o.finished:
                 sse.discard(rid)
             if o.new_token_ids and o.new_text and o.completion_tokens and not o.error:
-                o.sse = encode_sse_chunk(o.new_text, o.completion_tokens - 1, o.logprobs[-1] if o.logprobs else None)
+                top = top_logprob_dicts(self.engine.tokenizer, o.top_logprobs[-1]) if o.top_logprobs else None
+                o.sse = encode_sse_chunk(o.new_text, o.completion_tokens - 1, o.logprobs[-1] if o.logprobs else None,
+                                         top)
 
     def submit(self, cmd: tuple) -> None:
         self._inbox.put(cmd)
