@@ -108,10 +108,21 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const uint16_t* __restri
   }
 }
 
-static int pick_threads(int nchunk, int& vpt) {
-  int threads = nchunk >= 256 ? 256 : ((nchunk + 63) / 64) * 64;
+// The row kernels keep a whole row in registers: at most 256 threads x 8 chunks x 8
+// columns. A wider row would be truncated without a fault (the columns past the limit
+// neither read into the statistic nor written), so the bindings reject H outside
+// [norm_min_h(), norm_max_h()] before any launch. add_partials_rmsnorm
+// (skinny_gemm.hip) launches through norm_pick_threads too: one limit for all four.
+constexpr int kNormMaxThreads = 256, kNormMaxVpt = 8, kNormChunk = 8;
+
+int norm_min_h() { return kNormChunk; }
+int norm_max_h() { return kNormMaxThreads * kNormMaxVpt * kNormChunk; }
+
+// threads (64..256, whole waves) and VPT (1, 2, 4 or 8 chunks per thread) of a row of nchunk chunks
+int norm_pick_threads(int nchunk, int& vpt) {
+  int threads = nchunk >= kNormMaxThreads ? kNormMaxThreads : ((nchunk + 63) / 64) * 64;
   vpt = (nchunk + threads - 1) / threads;
-  vpt = vpt <= 1 ? 1 : vpt <= 2 ? 2 : vpt <= 4 ? 4 : 8;
+  vpt = vpt <= 1 ? 1 : vpt <= 2 ? 2 : vpt <= 4 ? 4 : kNormMaxVpt;
   return threads;
 }
 
@@ -119,7 +130,7 @@ template <bool FUSED>
 static void launch_rms(const uint16_t* x, uint16_t* res, const uint16_t* w, uint16_t* out, int T, int H,
                        float eps, int64_t xs, int64_t os, hipStream_t st) {
   int vpt;
-  int thr = pick_threads(H / 8, vpt);
+  int thr = norm_pick_threads(H / 8, vpt);
   dim3 g(T), b(thr);
   switch (vpt) {
     case 1: hipLaunchKernelGGL((rmsnorm_kernel<1, FUSED>), g, b, 0, st, x, res, w, out, H, eps, xs, os); break;
@@ -201,7 +212,7 @@ void layernorm(const uint16_t* x, const uint16_t* w, const uint16_t* b, uint16_t
                float eps, hipStream_t st) {
   if (T <= 0) return;
   int vpt;
-  int thr = pick_threads(H / 8, vpt);
+  int thr = norm_pick_threads(H / 8, vpt);
   dim3 g(T), blk(thr);
   switch (vpt) {
     case 1: hipLaunchKernelGGL(layernorm_kernel<1>, g, blk, 0, st, x, w, b, out, H, eps); break;

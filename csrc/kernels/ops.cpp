@@ -19,6 +19,8 @@ namespace xgk {
 void rmsnorm(const uint16_t*, const uint16_t*, uint16_t*, int, int, float, int64_t, int64_t, hipStream_t);
 void fused_add_rmsnorm(const uint16_t*, uint16_t*, const uint16_t*, uint16_t*, int, int, float, hipStream_t);
 void layernorm(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, int, int, float, hipStream_t);
+int norm_min_h();
+int norm_max_h();
 void silu_and_mul(const uint16_t*, uint16_t*, int, int, int, hipStream_t);
 int skinny_gemm(const uint16_t*, int, int, const uint16_t*, int, float*, uint16_t*, int, int, hipStream_t);
 int skinny_slab_kmax(int);
@@ -106,26 +108,39 @@ static void check(int rc, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// rmsnorm / fused_add_rmsnorm / layernorm / add_partials_rmsnorm hold a row in registers:
+// H outside [norm_min_h(), norm_max_h()] would be truncated silently (norm.hip)
+static void check_norm_h(int H, const char* what) {
+  if (H % 8 || H < xgk::norm_min_h() || H > xgk::norm_max_h())
+    throw std::invalid_argument(std::string(what) + ": H % 8 != 0 or H outside [" +
+                                std::to_string(xgk::norm_min_h()) + ", " + std::to_string(xgk::norm_max_h()) + "]");
+}
+
 PYBIND11_MODULE(_kernels, m) {
   m.doc() = "xgserve hand-written CDNA4 (gfx950) HIP kernels";
   m.attr("arch") = "gfx950";
+  m.def("norm_min_h", &xgk::norm_min_h);
+  m.def("norm_max_h", &xgk::norm_max_h);
 
   m.def("rmsnorm", [](uintptr_t x, uintptr_t w, uintptr_t out, int T, int H, float eps, int64_t xs, int64_t os,
                       uintptr_t st) {
-    if (H % 8) throw std::invalid_argument("rmsnorm: H % 8 != 0");
+    check_norm_h(H, "rmsnorm");
+    if (T <= 0) return;  // nothing to launch: no device call either
     xgk::rmsnorm(P<const uint16_t>(x), P<const uint16_t>(w), P<uint16_t>(out), T, H, eps, xs, os, S(st));
     check(0, "rmsnorm");
   });
   m.def("fused_add_rmsnorm", [](uintptr_t x, uintptr_t res, uintptr_t w, uintptr_t out, int T, int H, float eps,
                                 uintptr_t st) {
-    if (H % 8) throw std::invalid_argument("fused_add_rmsnorm: H % 8 != 0");
+    check_norm_h(H, "fused_add_rmsnorm");
+    if (T <= 0) return;  // nothing to launch: no device call either
     xgk::fused_add_rmsnorm(P<const uint16_t>(x), P<uint16_t>(res), P<const uint16_t>(w), P<uint16_t>(out), T, H,
                            eps, S(st));
     check(0, "fused_add_rmsnorm");
   });
   m.def("layernorm", [](uintptr_t x, uintptr_t w, uintptr_t b, uintptr_t out, int T, int H, float eps,
                         uintptr_t st) {
-    if (H % 8) throw std::invalid_argument("layernorm: H % 8 != 0");
+    check_norm_h(H, "layernorm");
+    if (T <= 0) return;  // nothing to launch: no device call either
     xgk::layernorm(P<const uint16_t>(x), P<const uint16_t>(w), P<const uint16_t>(b), P<uint16_t>(out), T, H, eps,
                    S(st));
     check(0, "layernorm");
@@ -145,7 +160,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("skinny_slab_kmax", &xgk::skinny_slab_kmax);
   m.def("add_partials_rmsnorm", [](uintptr_t part, int S_, int T, uintptr_t res, uintptr_t w, uintptr_t out, int H,
                                    float eps, uintptr_t st) {
-    if (H % 8) throw std::invalid_argument("add_partials_rmsnorm: H % 8 != 0");
+    check_norm_h(H, "add_partials_rmsnorm");
+    if (T <= 0) return;  // nothing to launch: no device call either
     xgk::add_partials_rmsnorm(P<const float>(part), S_, T, P<uint16_t>(res), P<const uint16_t>(w), P<uint16_t>(out),
                               H, eps, S(st));
     check(0, "add_partials_rmsnorm");

@@ -402,15 +402,16 @@ __global__ void __launch_bounds__(256) add_partials_rmsnorm_kernel(const float* 
   }
 }
 
+int norm_pick_threads(int nchunk, int& vpt);  // norm.hip
+
 void add_partials_rmsnorm(const float* part, int S, int T, uint16_t* residual, const uint16_t* w, uint16_t* out,
                           int H, float eps, hipStream_t st) {
   if (T <= 0) return;
-  const int nchunk = H / 8;
-  const int thr = nchunk >= 256 ? 256 : ((nchunk + 63) / 64) * 64;
-  const int vpt = (nchunk + thr - 1) / thr;  // chunks per thread: VPT = the next of 1, 2, 4, 8
+  int vpt;  // chunks per thread: 1, 2, 4 or 8 (norm.hip: the same row limits as rmsnorm)
+  const int thr = norm_pick_threads(H / 8, vpt);
   dim3 g(T), b(thr);
   sp_dispatch<1, 2, 4, 8>(S, [&](auto sp) {
-    cfg_dispatch<4>(vpt <= 1 ? 0 : vpt <= 2 ? 1 : vpt <= 4 ? 2 : 3, [&](auto lv) {
+    cfg_dispatch<4>(vpt == 1 ? 0 : vpt == 2 ? 1 : vpt == 4 ? 2 : 3, [&](auto lv) {
       hipLaunchKernelGGL((add_partials_rmsnorm_kernel<1 << decltype(lv)::value, decltype(sp)::value>), g, b, 0, st,
                          part, S, T, residual, w, out, H, eps);
     });
