@@ -157,7 +157,12 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     gh (tests / A/B sweeps; None = the kernel's own choice): > 0 runs the 16-row
     kernel with gh query heads per workgroup; < 0 forces a D = 128 prefill_attn2_kernel
     configuration -gh = 1000 (KS - 1) + 100 NSLOT + 10 NW + GH (key phases, ring
-    slots, waves, heads per workgroup; NSLOT 0 = default), e.g. -82 or -1284."""
+    slots, waves, heads per workgroup; NSLOT 0 = default), e.g. -82 or -1284.
+    Only the T = query_start_loc[-1] packed rows are written: a sequence with q_len == 0
+    has no row and launches nothing, and rows of a larger buffer that `out` is a slice of
+    keep their contents. max_q_len sizes the grid and may exceed every real length (the
+    engine passes a padded value). As in decode_attention, cache rows past a sequence's
+    end may hold anything, NaN and Inf included."""
     if not use_native(q):
         r = prefill_attention_ref(q, k_cache, v_cache, block_tables, query_start_loc, seq_lens, scale)
         if out is not None:
