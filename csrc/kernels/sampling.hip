@@ -9,18 +9,9 @@
 //     (<= 24 passes), no sort;
 //   * the draw is Gumbel-max: argmax(logit/T - log(-log u)), u from a
 //     per-(seed, step, row, index) counter hash, so a fixed seed reproduces.
-#include "glds.h"
+#include "samp_common.h"  // hash32, VecW, scalar_at: shared with spec_sample.hip
 
 namespace xgk {
-
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
 
 template <typename T>
 __device__ __forceinline__ int load_vec(const T* row, int i, float* f);
@@ -36,14 +27,6 @@ __device__ __forceinline__ int load_vec<float>(const float* row, int i, float* f
   f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
   return 4;
 }
-template <typename T> struct VecW { static constexpr int W = 8; };
-template <> struct VecW<float> { static constexpr int W = 4; };
-
-template <typename T>
-__device__ __forceinline__ float scalar_at(const T* row, int i);
-template <> __device__ __forceinline__ float scalar_at<uint16_t>(const uint16_t* r, int i) { return bf2f(r[i]); }
-template <> __device__ __forceinline__ float scalar_at<float>(const float* r, int i) { return r[i]; }
-
 // reduce (val, idx) max with lowest index on ties, plus (m, s) log-sum-exp
 struct ArgLse {
   float v; int i; float m; float s;

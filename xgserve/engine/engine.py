@@ -50,6 +50,19 @@ EARLY_OUTPUTS = True
 _MASK63 = (1 << 63) - 1
 
 
+def position_seeds(seed: np.ndarray, n: np.ndarray) -> np.ndarray:
+    """The sampling seed of output token n of a request with base seed `seed` (uint64
+    arrays -> int64): the counter-based per-request stream, mix(seed, n). Every sampler
+    call of a position takes it, on the target and on a speculating draft."""
+    with np.errstate(over="ignore"):
+        x = seed.astype(np.uint64) * np.uint64(6364136223846793005) + (n.astype(np.uint64) + np.uint64(1)) * np.uint64(
+            1442695040888963407)
+        x &= np.uint64(_MASK63)
+        x ^= x >> np.uint64(29)
+        x = (x * np.uint64(0xBF58476D1CE4E5B9)) & np.uint64(_MASK63)
+    return x.view(np.int64)
+
+
 @dataclass
 class EngineConfig:
     model: str = "llama3-8b"
@@ -86,6 +99,9 @@ class EngineConfig:
     draft_model: Optional[str] = None
     num_speculative_tokens: int = 0
     spec_min_acceptance_rate: float = 0.5
+    # speculate sampled requests too (temperature > 0 without top-p / top-k), verified by
+    # rejection sampling (ops.spec_verify_sample); off: they run as plain decodes
+    spec_sampled: bool = False
     # detokenise / build step N's outputs while step N+1 runs on the GPU (first
     # tokens are still emitted at once, so TTFT is unchanged)
     overlap_outputs: bool = True
@@ -240,7 +256,7 @@ class LLMEngine:
         if cfg.draft_model and cfg.num_speculative_tokens > 0:
             from .spec_decode import SpeculativeDecoder
             self.spec = SpeculativeDecoder(self, cfg.draft_model, cfg.num_speculative_tokens,
-                                           cfg.spec_min_acceptance_rate)
+                                           cfg.spec_min_acceptance_rate, sampled=cfg.spec_sampled)
         self._inflight = None  # (plan, handle): launched by the previous step() (async scheduling)
         # Speculative decoding keeps the synchronous loop: asynchronous scheduling plans
         # step N+1 before step N's tokens reach the host, which needs every row's next
@@ -444,13 +460,7 @@ class LLMEngine:
         if n is None:
             seeds = self.slot_seed[slots].view(np.int64)
         else:
-            with np.errstate(over="ignore"):
-                x = self.slot_seed[slots] * np.uint64(6364136223846793005) + (n + np.uint64(1)) * np.uint64(
-                    1442695040888963407)
-                x &= np.uint64(_MASK63)
-                x ^= x >> np.uint64(29)
-                x = (x * np.uint64(0xBF58476D1CE4E5B9)) & np.uint64(_MASK63)
-            seeds = x.view(np.int64)
+            seeds = position_seeds(self.slot_seed[slots], n)
         samp = SamplingRows(temps, self.slot_topp[slots], self.slot_topk[slots], seeds)
         if self.slot_topn[slots].any():
             samp.topn = self.slot_topn[slots]
@@ -894,7 +904,7 @@ class LLMEngine:
             "memory_available": (self.sched.num_free_blocks() + self.sched.num_evictable_blocks()) * bb,
             "memory_limit": int(self.sched.num_blocks() * bb * self.cfg.cache_threshold),
             "weight_bytes": self._weight_bytes,
-            "scratch_bytes": self._scratch_bytes,
+            "scratch_bytes": self._scratch_bytes + (self.spec.scratch_bytes() if self.spec is not None else 0),
             "weight_dtype": getattr(self.model, "weight_dtype", None) or str(self.model.dtype).replace("torch.", ""),
             "cache": cs,
             "preemptions": self.sched.total_preemptions(),

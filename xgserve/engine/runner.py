@@ -48,6 +48,20 @@ log = logging.getLogger("xgserve.runner")
 
 
 @dataclass
+class SpecVerifyRows:
+    """The sampled verify blocks of a step (ops.spec_verify_sample), host arrays per block:
+    first logits row of the step (in sample order), first row of the draft's kept logits,
+    draft tokens (ks[j] each, concatenated), temperature; one seed per position."""
+    p_row0: np.ndarray
+    q_row0: np.ndarray
+    ks: np.ndarray
+    temps: np.ndarray
+    seeds: np.ndarray
+    draft: np.ndarray
+    q_logits: torch.Tensor
+
+
+@dataclass
 class SamplingRows:
     """Per-row sampling parameters (host numpy arrays), aligned with logits rows."""
     temps: np.ndarray
@@ -65,6 +79,9 @@ class SamplingRows:
     # top-N alternatives (ops.top_logprobs): int32 entries asked per row, None: no row asked
     # and the step enqueues nothing for them
     topn: Optional[np.ndarray] = None
+    # speculative sampling: after the step's sampler ran over every row, these blocks' rows
+    # are overwritten by the rejection-sampling verification; None: nothing is enqueued
+    spec: Optional[SpecVerifyRows] = None
 
     @property
     def all_greedy(self) -> bool:
@@ -164,6 +181,14 @@ class ModelRunner:
         self.top_result = None        # per sampled row of the step wait() last returned: [(id, lp)] or None
         self._top_last = None
         self._top_pending: Dict[int, tuple] = {}
+        # speculative sampling: accepted[j] of the step's sampled verify blocks, riding the
+        # step's D2H set and event like the top-N results (nothing exists until a step asks)
+        self.h_acc = None
+        self.spec_result = None       # int32 per sampled block of the step wait() last returned, or None
+        self._spec_last = None
+        self._spec_pending: Dict[int, tuple] = {}
+        self.sampler_logits = None    # what the last step's sampler read, in sample order
+        self.keep_sampler_logits = False  # eager steps too (a speculating draft): holds the tensor a step longer
         self._es_pin = [None, None]   # eager-step sampling rows: pinned stagings + events
         self._es_ev = [None, None]
         self._es_idx = 0
@@ -582,9 +607,12 @@ class ModelRunner:
         row of the previous GRAPH step whose sampled token is this row's input
         (-1: the plan's own id)."""
         self._top_last = None
+        self._spec_last = None
         h = self._launch(plan, samp, src)
         if self._top_last is not None:
             self._top_pending[id(h)] = (h, self._top_last)  # the handle is held: its id stays its own
+        if self._spec_last is not None:
+            self._spec_pending[id(h)] = (h, self._spec_last)
         return h
 
     def _launch(self, plan: dict, samp: Optional[SamplingRows], src: Optional[np.ndarray]):
@@ -718,7 +746,41 @@ class ModelRunner:
     def wait(self, handle):
         res = self._wait(handle)
         self.top_result = self._top_collect(handle) if self._top_pending else None
+        self.spec_result = self._spec_collect(handle) if self._spec_pending else None
         return res
+
+    # ------------------------------------------------------------------ speculative sampling
+    def last_sampler_logits(self) -> Optional[torch.Tensor]:
+        """The logits rows the last launched step's sampler read, in sample order (a graph
+        step's static buffer: valid until the next replay of that graph; eager steps keep
+        theirs only under keep_sampler_logits)."""
+        return self.sampler_logits
+
+    def _spec_launch(self, logits: torch.Tensor, tok: torch.Tensor, lp: torch.Tensor, sv: SpecVerifyRows) -> None:
+        """ops.spec_verify_sample over the step's sampled verify blocks: overwrites their
+        rows of tok / lp in place; accepted[j] leaves with the step's output set (queued in
+        front of the token copy, covered by the event wait() waits on)."""
+        nb = len(sv.ks)
+        d_off = np.concatenate([[0], np.cumsum(sv.ks)[:-1]])
+        _, _, acc = ops.spec_verify_sample(logits, sv.q_logits, sv.draft, sv.p_row0, sv.q_row0, d_off, sv.ks, sv.temps,
+                                           sv.seeds, out_row0=sv.p_row0, out_tok=tok, out_lp=lp)
+        if not self.is_cuda:
+            self._spec_last = (acc.numpy().copy(),)
+            return
+        if self.h_acc is None:
+            self.h_acc = [_pinned(max(self.max_num_seqs, self.max_tokens), torch.int32) for _ in range(2)]
+        i = self.out_idx
+        self.h_acc[i][:nb].copy_(acc, non_blocking=True)
+        self._spec_last = (i, nb)
+
+    def _spec_collect(self, handle):
+        p = self._spec_pending.pop(id(handle), None)
+        if p is None:
+            return None
+        if len(p[1]) == 1:
+            return p[1][0]
+        i, nb = p[1]
+        return self.h_acc[i][:nb].numpy().copy()
 
     def _wait(self, handle):
         n, hidden, ready, out = handle[:4]
@@ -776,6 +838,7 @@ class ModelRunner:
         ev.record()
         self.g_stage_events[si] = ev
         graph.replay()
+        self.sampler_logits = graph.xgs_logits
         if samp is not None and samp.topn is not None:
             self._top_launch(graph.xgs_logits, samp)
         self._log_samples(n)
@@ -836,6 +899,7 @@ class ModelRunner:
         ev.record()
         self.g_stage_events[si] = ev
         graph.replay()
+        self.sampler_logits = graph.xgs_logits
         if samp is not None and samp.topn is not None:
             self._top_launch(graph.xgs_logits, samp)
         self.mixed_replays += 1
@@ -982,6 +1046,8 @@ class ModelRunner:
             tok, lp = ops.sample_tokens(out, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
         if self.p_state is not None:
             ops.logit_state_update(self.p_state, d_pi[0], tok, n)
+        if self.keep_sampler_logits:
+            self.sampler_logits = out
         if samp.topn is not None:
             self._top_launch(out, samp)
         return tok, lp
@@ -1022,6 +1088,10 @@ class ModelRunner:
             seeds = torch.from_numpy(samp.seeds.astype(np.int64))
             gen = torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
             tok, lp = ops.sample_tokens(logits, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
+        if self.keep_sampler_logits:
+            self.sampler_logits = logits
+        if samp is not None and samp.spec is not None:
+            self._spec_launch(logits, tok, lp, samp.spec)
         if samp is not None and samp.topn is not None:
             self._top_launch(logits, samp)
         return tok, lp

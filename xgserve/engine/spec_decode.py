@@ -24,9 +24,19 @@ from exponential moving averages of both (None until both kinds were seen).
 
 Acceptance is tracked per request and globally; a request whose acceptance rate
 stays below `min_acceptance_rate` (0.5, requirements.md:170) after a few
-verifies stops speculating (its draft pages are freed). Sampled (temperature >
-0) requests are not speculated: greedy verification is exact, and they simply
-run as plain decodes in the same batches.
+verifies stops speculating (its draft pages are freed).
+
+Sampled requests (temperature > 0) are speculated only with `sampled=True`
+(spec.sampled) and only without top-p / top-k: the draft DRAWS its tokens (its
+sampler, stream 0 of the position's seed), the logits rows it drew from are kept
+(the definition of q), and the verify step runs ops.spec_verify_sample over those
+blocks after its sampler: draft token i is accepted with probability
+min(1, p(d)/q(d)), the first rejected position emits a token of the residual
+norm(max(0, p - q)), a fully accepted block a bonus token of p -- the output
+follows the target's distribution whatever the draft says. A fixed seed
+reproduces on the same configuration but, unlike greedy, does not equal the
+non-speculating engine's output. Otherwise sampled requests run as plain decodes
+in the same batches.
 
 TP > 1: the draft lives only on the leader (TP=1 weights); followers execute the
 verify plan broadcast with every other step.
@@ -41,7 +51,7 @@ import numpy as np
 import torch
 
 from .request import RequestType
-from .runner import ModelRunner, SamplingRows
+from .runner import ModelRunner, SamplingRows, SpecVerifyRows
 
 log = logging.getLogger("xgserve.spec")
 
@@ -58,17 +68,22 @@ class _DraftSeq:
     accepted: int = 0
     verifies: int = 0
     disabled: bool = False
+    q_row0: int = -1         # sampled proposal of this round: first row of the kept draft logits
 
 
 class SpeculativeDecoder:
-    def __init__(self, engine, draft_model: str, k: int, min_acceptance_rate: float = 0.5):
+    def __init__(self, engine, draft_model: str, k: int, min_acceptance_rate: float = 0.5, sampled: bool = False):
         from ..models import build_model, get_config
         self.engine = engine
         self.k = int(k)
         self.min_acceptance_rate = min_acceptance_rate
         self.enabled = engine.is_driver
+        self.sampled = bool(sampled)
         self.proposed = 0
         self.accepted = 0
+        self.sampled_proposed = 0   # the part of proposed / accepted that sampled blocks contributed
+        self.sampled_accepted = 0
+        self.q_buf: Optional[torch.Tensor] = None  # [max_num_seqs * k, V] draft logits rows of sampled proposals
         self.verifies = 0
         self.seqs: Dict[int, _DraftSeq] = {}
         self.ema_spec_ms: Optional[float] = None   # step time with verify rows (propose + verify)
@@ -92,6 +107,7 @@ class SpeculativeDecoder:
         self.runner = ModelRunner(self.model, block_size=bs, num_blocks=nblocks, max_num_seqs=ec.max_num_seqs,
                                   max_num_batched_tokens=ec.max_num_batched_tokens, max_model_len=engine.max_model_len,
                                   use_graphs=ec.use_graphs, graph_batch_sizes=ec.graph_batch_sizes, is_driver=True)
+        self.runner.keep_sampler_logits = self.sampled
         self.runner.capture_graphs()
         self.free: List[int] = list(range(nblocks - 1, -1, -1))
         log.info("speculative decoding: draft=%s k=%d draft KV pages=%d", draft_model, self.k, nblocks)
@@ -140,11 +156,50 @@ class SpeculativeDecoder:
         sf = self.speedup_factor()
         return {"draft_tokens_proposed": self.proposed, "draft_tokens_accepted": self.accepted,
                 "acceptance_rate": self.accepted / self.proposed if self.proposed else 0.0,
+                "sampled_draft_tokens_proposed": self.sampled_proposed,
+                "sampled_draft_tokens_accepted": self.sampled_accepted,
                 "verify_steps": self.verifies,
                 "mean_tokens_per_verify": (self.accepted + self.verifies) / self.verifies if self.verifies else 0.0,
                 "spec_step_ms": self.ema_spec_ms, "plain_decode_step_ms": self.ema_plain_ms,
                 "speedup_factor": None if sf is None else round(sf, 4),
                 "active": sum(1 for d in self.seqs.values() if not d.disabled)}
+
+    def scratch_bytes(self) -> int:
+        return 0 if self.q_buf is None else self.q_buf.numel() * self.q_buf.element_size()
+
+    def _eligible_sampled(self, p) -> bool:
+        return self.sampled and p.temperature > 0 and p.top_p >= 1.0 and p.top_k == 0
+
+    def _draft_samp(self, order, sampled: dict, step: int) -> Optional[SamplingRows]:
+        """Sampling rows of a draft step, in its sample order: sampled sequences draw at
+        their temperature (no top-p / top-k) from the seed of output token n + step, the
+        engine's mix; greedy ones keep temperature 0. None: every row is greedy."""
+        from .engine import position_seeds
+        if not any(id(ds) in sampled for ds in order):
+            return None
+        ns = len(order)
+        temps, base, n = np.zeros(ns, np.float32), np.zeros(ns, np.uint64), np.zeros(ns, np.uint64)
+        for i, ds in enumerate(order):
+            e = sampled.get(id(ds))
+            if e is not None:
+                temps[i], base[i], n[i] = e[1], e[2], e[3] + step
+        return SamplingRows(temps, np.ones(ns, np.float32), np.zeros(ns, np.int32), position_seeds(base, n))
+
+    def _keep_q(self, order, sampled: dict, step: int) -> None:
+        """Copy the logits rows the draft sampler just read for the sampled sequences
+        into their rows of q_buf (row q_row0 + step): with sample_tokens, the definition
+        of q -- the verify kernel recomputes y_q from exactly these rows."""
+        src = [i for i, ds in enumerate(order) if id(ds) in sampled]
+        if not src:
+            return
+        logits = self.runner.last_sampler_logits()
+        if self.q_buf is None:  # lazily, at the first sampled proposal
+            self.q_buf = torch.zeros(self.engine.cfg.max_num_seqs * self.k, logits.shape[1], dtype=logits.dtype,
+                                     device=logits.device)
+        dst = [sampled[id(order[i])][0] + step for i in src]
+        dev = logits.device
+        self.q_buf.index_copy_(0, torch.tensor(dst, dtype=torch.long, device=dev),
+                               logits.index_select(0, torch.tensor(src, dtype=torch.long, device=dev)))
 
     # ------------------------------------------------------------------ draft steps
     def _plan(self, rows) -> dict:
@@ -185,11 +240,17 @@ class SpeculativeDecoder:
             self._release(sid)
         budget = self.runner.max_tokens
         rows, ready = [], []
+        for sid, ds in self.seqs.items():
+            if ds.q_row0 >= 0:
+                # a sampled proposal the scheduler has not verified: its q rows are about to be
+                # reused, so the draft is withdrawn (re-proposed below if still eligible)
+                ds.q_row0 = -1
+                eng.sched.set_draft(sid, [])
         for sid, req in eng.by_seq.items():
             if req.finished or req.kind == RequestType.Embeddings or not req.output_ids:
                 continue
             p = req.params
-            if p.temperature > 0 or len(req.output_ids) + 1 >= p.max_tokens:
+            if (p.temperature > 0 and not self._eligible_sampled(p)) or len(req.output_ids) + 1 >= p.max_tokens:
                 continue
             ds = self.seqs.get(sid)
             if ds is None:
@@ -223,23 +284,35 @@ class SpeculativeDecoder:
                 ready.append((sid, ds, L))
         if not rows:
             return
+        # sampled sequences of this round: id(ds) -> (first q_buf row, temperature, seed, n)
+        sampled = {}
+        for sid, ds, _ in ready:
+            req = eng.by_seq[sid]
+            if req.params.temperature > 0:
+                sampled[id(ds)] = (len(sampled) * self.k, req.params.temperature, req.params.seed & ((1 << 63) - 1),
+                                   len(req.output_ids))
         plan = self._plan(rows)
-        toks, _, _ = self.runner.execute(plan, None)
+        order = [r[0] for r in plan["order"] if r[3]]
+        toks, _, _ = self.runner.execute(plan, self._draft_samp(order, sampled, 0))
         if not ready:
             return
-        order = [r[0] for r in plan["order"] if r[3]]
+        self._keep_q(order, sampled, 0)
         first = {id(ds): int(t) for ds, t in zip(order, toks)}
         drafts = {sid: [first[id(ds)]] for sid, ds, _ in ready}
         for step in range(1, self.k):
             drows = [(ds, [drafts[sid][-1]], L + step - 1, True) for sid, ds, L in ready]
             dplan = self._plan(drows)
-            t2, _, _ = self.runner.execute(dplan, None)
+            dorder = [r[0] for r in dplan["order"]]
+            t2, _, _ = self.runner.execute(dplan, self._draft_samp(dorder, sampled, step))
+            self._keep_q(dorder, sampled, step)
             by_ds = {id(r[0]): int(t) for r, t in zip(dplan["order"], t2)}
             for sid, ds, _ in ready:
                 drafts[sid].append(by_ds[id(ds)])
         for sid, ds, L in ready:
             ds.computed = L + self.k - 1
             ds.pending_L, ds.pending_k = L, self.k
+            e = sampled.get(id(ds))
+            ds.q_row0 = -1 if e is None else e[0]
             eng.sched.set_draft(sid, drafts[sid])
 
     # ------------------------------------------------------------------ verify
@@ -251,19 +324,26 @@ class SpeculativeDecoder:
         nrows = np.array([int(q_lens[s]) if (not is_pre[s] and q_lens[s] > 1) else 1 for s in sidx.tolist()],
                          dtype=np.int64)
         rsamp = None
+        qsl, ids, seq_ids = plan["query_start_loc"], plan["input_ids"], plan["seq_ids"]
+        sblock = {}  # index j of a sampled verify block -> its index among the step's sampled blocks
         if samp is not None:
+            seeds = np.repeat(samp.seeds, nrows)
+            if self.sampled and self.q_buf is not None:
+                sv = self._sampled_blocks(plan, samp, nrows, seeds, sblock)
+            else:
+                sv = None
             rsamp = SamplingRows(np.repeat(samp.temps, nrows), np.repeat(samp.top_ps, nrows),
-                                 np.repeat(samp.top_ks, nrows), np.repeat(samp.seeds, nrows))
+                                 np.repeat(samp.top_ks, nrows), seeds, spec=sv)
             if samp.topn is not None:
                 rsamp.topn = np.repeat(samp.topn, nrows)
         toks, lps, hidden = self.engine.runner.execute(plan, rsamp)
         if toks is None:
             return None, None, hidden, None
+        acc = self.engine.runner.spec_result  # accepted[b] of the sampled blocks, same D2H and event as toks
         out_t, out_l, counts = [], [], []
         tops = self.engine.runner.top_result  # per verify row; sliced to the accepted positions as lps
         out_top = [] if tops is not None else None
         k = 0
-        qsl, ids, seq_ids = plan["query_start_loc"], plan["input_ids"], plan["seq_ids"]
         for j, s in enumerate(sidx.tolist()):
             n_r = int(nrows[j])
             if n_r == 1:
@@ -277,25 +357,70 @@ class SpeculativeDecoder:
             draft = ids[int(qsl[s]) + 1:int(qsl[s]) + n_r]
             t = toks[k:k + n_r]
             n = 0
-            while n < n_r - 1 and int(draft[n]) == int(t[n]):
-                n += 1
+            sampled = samp is not None and samp.temps[j] > 0
+            if j in sblock:
+                # rejection sampling ran on the device: rows [0, n] hold the accepted draft
+                # tokens and the residual / bonus token
+                n = int(acc[sblock[j]])
+            elif not sampled:
+                while n < n_r - 1 and int(draft[n]) == int(t[n]):
+                    n += 1
+            # (a sampled block without kept draft logits takes the target's own draw of row 0)
             out_t.extend(int(x) for x in t[:n + 1])  # accepted drafts == target tokens, + the bonus token
             out_l.extend(float(x) for x in lps[k:k + n + 1])
             counts.append(n + 1)
             if tops is not None:
                 out_top.extend(tops[k:k + n + 1])
             k += n_r
-            self._account(int(seq_ids[s]), n_r - 1, n)
+            self._account(int(seq_ids[s]), n_r - 1, n, sampled)
         plan["_top"] = out_top
         return (np.asarray(out_t, np.int32), np.asarray(out_l, np.float32), hidden, np.asarray(counts, np.int32))
 
-    def _account(self, sid: int, proposed: int, accepted: int) -> None:
+    def _sampled_blocks(self, plan: dict, samp: SamplingRows, nrows: np.ndarray, seeds: np.ndarray,
+                        sblock: dict) -> Optional[SpecVerifyRows]:
+        """The step's sampled verify blocks (proposed this round, their q rows kept):
+        fills their per-position seeds (output tokens n .. n + k of the request) into
+        `seeds` and their order into `sblock`."""
+        from .engine import position_seeds
+        sidx, seq_ids, qsl, ids = plan["sample_seq_index"], plan["seq_ids"], plan["query_start_loc"], plan["input_ids"]
+        row0 = np.concatenate([[0], np.cumsum(nrows)[:-1]])
+        p0, q0, ks, temps, pseeds, draft = [], [], [], [], [], []
+        for j, s in enumerate(sidx.tolist()):
+            n_r = int(nrows[j])
+            if n_r == 1 or not samp.temps[j] > 0:
+                continue
+            sid = int(seq_ids[s])
+            ds, req = self.seqs.get(sid), self.engine.by_seq.get(sid)
+            if ds is None or req is None or ds.q_row0 < 0 or n_r - 1 > self.k:
+                continue
+            r0 = int(row0[j])
+            ps = position_seeds(np.full(n_r, req.params.seed & ((1 << 63) - 1), np.uint64),
+                                len(req.output_ids) + np.arange(n_r, dtype=np.uint64))
+            seeds[r0:r0 + n_r] = ps
+            sblock[j] = len(ks)
+            p0.append(r0)
+            q0.append(ds.q_row0)
+            ks.append(n_r - 1)
+            temps.append(samp.temps[j])
+            pseeds.append(ps)
+            draft.append(ids[int(qsl[s]) + 1:int(qsl[s]) + n_r])
+        if not ks:
+            return None
+        return SpecVerifyRows(np.asarray(p0, np.int64), np.asarray(q0, np.int64), np.asarray(ks, np.int64),
+                              np.asarray(temps, np.float32), np.concatenate(pseeds),
+                              np.concatenate(draft).astype(np.int32), self.q_buf)
+
+    def _account(self, sid: int, proposed: int, accepted: int, sampled: bool = False) -> None:
         self.proposed += proposed
         self.accepted += accepted
         self.verifies += 1
+        if sampled:
+            self.sampled_proposed += proposed
+            self.sampled_accepted += accepted
         ds = self.seqs.get(sid)
         if ds is None:
             return
+        ds.q_row0 = -1  # verified: the q rows are free again
         if ds.pending_L >= 0:
             ds.computed = ds.pending_L + min(accepted, ds.pending_k - 1)
             ds.pending_L = -1

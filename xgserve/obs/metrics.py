@@ -75,6 +75,8 @@ class MetricsCollector:
         self.workers: Dict[int, dict] = {}
         self.spec_proposed = 0
         self.spec_accepted = 0
+        self.spec_sampled_proposed = 0
+        self.spec_sampled_accepted = 0
         self.spec_speedup: Optional[float] = None
         self._recent_lat: deque = deque(maxlen=4096)
         self._tok_events: deque = deque()  # (t, prompt, gen)
@@ -173,11 +175,14 @@ class MetricsCollector:
         with self._lock:
             self.rejected_total[reason] += 1
 
-    def set_spec_totals(self, proposed: int, accepted: int, speedup: Optional[float] = None):
-        """Absolute draft-token counters (summed over replicas' heartbeats) and the
-        measured speculation speedup factor (mean over replicas that report one)."""
+    def set_spec_totals(self, proposed: int, accepted: int, speedup: Optional[float] = None,
+                        sampled_proposed: int = 0, sampled_accepted: int = 0):
+        """Absolute draft-token counters (summed over replicas' heartbeats), the part of
+        them that sampled (rejection-sampling) blocks contributed, and the measured
+        speculation speedup factor (mean over replicas that report one)."""
         with self._lock:
             self.spec_proposed, self.spec_accepted = proposed, accepted
+            self.spec_sampled_proposed, self.spec_sampled_accepted = sampled_proposed, sampled_accepted
             self.spec_speedup = speedup
 
     # ---- snapshot (design.md:480-491) -------------------------------------
@@ -213,7 +218,9 @@ class MetricsCollector:
                 "rejections": dict(self.rejected_total),
                 "speculative": {"proposed": self.spec_proposed, "accepted": self.spec_accepted,
                                 "acceptance_rate": self.spec_accepted / self.spec_proposed
-                                if self.spec_proposed else 0.0, "speedup_factor": self.spec_speedup},
+                                if self.spec_proposed else 0.0, "speedup_factor": self.spec_speedup,
+                                "sampled_draft_tokens_proposed": self.spec_sampled_proposed,
+                                "sampled_draft_tokens_accepted": self.spec_sampled_accepted},
                 "token_delivery_ms": _pcts(self._recent_delivery),
                 "event_loop_lag_ms": _pcts(self._recent_loop_lag),
                 "uptime_s": now - self.start,

@@ -13,6 +13,7 @@ from .attention import (decode_attention, decode_attention_fused, prefill_attent
                         prefill_attention_ref, choose_num_splits)
 from .sampling import argmax_logprob, sample_tokens, argmax_logprob_ref, segment_sum, subst_tokens
 from .sampling import top_logprobs, top_logprobs_ref, TOPLP_MAX
+from .sampling import spec_verify_sample
 from .sampling import (process_logits, process_scratch, logit_state_alloc, logit_state_cells, logit_state_reset,
                        logit_state_update, pack_state_resets, LOGIT_BIAS_MAX)
 from .embedding import embed_gather, mean_l2norm_rows
@@ -26,6 +27,7 @@ __all__ = [
     "RotaryCache", "rope_cache", "rope_cache_ref", "build_cos_sin",
     "decode_attention", "decode_attention_fused", "prefill_attention", "decode_attention_ref", "prefill_attention_ref", "choose_num_splits",
     "argmax_logprob", "sample_tokens", "argmax_logprob_ref", "segment_sum", "subst_tokens",
+    "spec_verify_sample",
     "process_logits", "process_scratch", "logit_state_alloc", "logit_state_cells", "logit_state_reset",
     "logit_state_update", "pack_state_resets", "LOGIT_BIAS_MAX",
     "embed_gather", "mean_l2norm_rows",

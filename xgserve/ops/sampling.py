@@ -1,6 +1,7 @@
 """K9 sampling + K11 pooling helpers."""
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -215,6 +216,216 @@ def _sample_workspace(device, B: int) -> torch.Tensor:
         # earlier (smaller) workspaces stay alive: captured graphs may still use them
         wss.append(torch.zeros(max(B, 256), row // 8, dtype=torch.int64, device=device))
     return wss[-1]
+
+
+# ---------------------------------------------------------------------------
+# Speculative sampling (csrc/kernels/spec_sample.hip): rejection-sampling verification
+# of sampled verify blocks. The contract (streams, accept test, residual and bonus draws)
+# is written at the head of that file; the CPU path below implements it in float64 with
+# the same counter hash, so a seed gives the same tokens wherever float rounding does not
+# decide.
+# ---------------------------------------------------------------------------
+_SPEC_WS = {}
+_M32 = 0xFFFFFFFF
+
+
+def _hash32i(x: int) -> int:
+    x &= _M32
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M32
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M32
+    return x ^ (x >> 16)
+
+
+def _hash32v(x):
+    import numpy as np
+    m = np.uint64(_M32)
+    x = x & m
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & m
+    return x ^ (x >> np.uint64(16))
+
+
+def _stream_key(seed: int, step: int) -> int:
+    seed &= (1 << 64) - 1
+    return _hash32i((seed & _M32) ^ _hash32i((seed >> 32) + 0x85EBCA6B)
+                    ^ _hash32i((step & _M32) * 0x27D4EB2F + 0x165667B1))
+
+
+def _gumbel_row(key: int, V: int):
+    """g(x) = -log(-log u(x)), u = ((hash >> 9) + 0.5) / 2^23, for x in [0, V)."""
+    import numpy as np
+    i = np.arange(V, dtype=np.uint64)
+    h = _hash32v(np.uint64(key) ^ _hash32v((i * np.uint64(0x9E3779B9)) & np.uint64(_M32)))
+    u = ((h >> np.uint64(9)).astype(np.float64) + 0.5) / 8388608.0
+    return -np.log(-np.log(u))
+
+
+def _spec_blocks(p_rows, q_rows, n_draft, n_out, V, p_row0, q_row0, d_off, ks, temps, out_row0):
+    """Checked int64 / float32 block arrays + (lrow0, Lp, Lq); ValueError on anything the
+    kernels would index out of range."""
+    import numpy as np
+    ks = np.asarray(ks, np.int64).reshape(-1)
+    nb = ks.shape[0]
+    p_row0, q_row0, d_off = (np.asarray(a, np.int64).reshape(-1) for a in (p_row0, q_row0, d_off))
+    temps = np.asarray(temps, np.float32).reshape(-1)
+    if V <= 0:
+        raise ValueError("spec_verify_sample: V must be positive")
+    if not (p_row0.shape[0] == q_row0.shape[0] == d_off.shape[0] == temps.shape[0] == nb):
+        raise ValueError("spec_verify_sample: per-block arrays differ in length")
+    if nb and ks.min() < 1:
+        raise ValueError("spec_verify_sample: a block has k < 1")
+    lrow0 = np.concatenate([[0], np.cumsum(ks + 1)[:-1]]) if nb else np.zeros(0, np.int64)
+    out_row0 = lrow0 if out_row0 is None else np.asarray(out_row0, np.int64).reshape(-1)
+    Lp, Lq = int((ks + 1).sum()), int(ks.sum())
+    if nb:
+        if Lp > 65535:
+            raise ValueError("spec_verify_sample: more than 65535 target rows")
+        if not (np.isfinite(temps).all() and (temps > 0).all()):
+            raise ValueError("spec_verify_sample: temperatures must be positive and finite")
+        if p_row0.min() < 0 or (p_row0 + ks + 1).max() > p_rows or q_row0.min() < 0 or (q_row0 + ks).max() > q_rows:
+            raise ValueError("spec_verify_sample: a block leaves the logits rows")
+        if d_off.min() < 0 or (d_off + ks).max() > n_draft:
+            raise ValueError("spec_verify_sample: a block leaves the draft tokens")
+        if out_row0.shape[0] != nb or out_row0.min() < 0 or (out_row0 + ks + 1).max() > n_out:
+            raise ValueError("spec_verify_sample: a block leaves the output rows")
+    return p_row0, q_row0, d_off, ks, temps, lrow0, out_row0, Lp, Lq
+
+
+def _spec_verify_ref(p_logits, q_logits, draft, p_row0, q_row0, d_off, ks, temps, lrow0, out_row0, seeds, out_tok,
+                     out_lp, accepted) -> None:
+    import numpy as np
+    P = p_logits.detach().float().cpu().numpy()
+    Q = q_logits.detach().float().cpu().numpy()
+    V = P.shape[1]
+    rows = {}
+
+    def row(which, r, t):  # (y float64, logZ) of a logits row under temperature t, computed once
+        key = (which, r, t.tobytes())
+        v = rows.get(key)
+        if v is None:
+            x = (P if which == 0 else Q)[r]
+            y = (x * (np.float32(1) / t)).astype(np.float32).astype(np.float64)
+            m = y.max()
+            v = rows[key] = (y, m + np.log(np.exp(y - m).sum()))
+        return v
+
+    ot, ol, ac = out_tok.numpy(), out_lp.numpy(), accepted.numpy()
+    with np.errstate(all="ignore"):
+        for j in range(ks.shape[0]):
+            k, t = int(ks[j]), temps[j]
+            a = k
+            for i in range(k + 1):
+                seed = int(seeds[lrow0[j] + i])
+                yp, zp = row(0, int(p_row0[j]) + i, t)
+                o = int(out_row0[j]) + i
+                if i < k:
+                    d = int(draft[d_off[j] + i])
+                    yq, zq = row(1, int(q_row0[j]) + i, t)
+                    ok = False
+                    if 0 <= d < V:
+                        u = ((_hash32i(_stream_key(seed, 1)) >> 9) + 0.5) / 8388608.0
+                        ok = math.log(u) + (yq[d] - zq) <= yp[d] - zp
+                    if ok:
+                        ot[o], ol[o] = d, yp[d] - zp
+                        continue
+                    a = i
+                    lp, lq = yp - zp, yq - zq
+                    keep = lp > lq
+                    if keep.any():
+                        score = np.where(keep, lp + np.log(-np.expm1(np.where(keep, lq - lp, -1.0)))
+                                         + _gumbel_row(_stream_key(seed, 2), V), -np.inf)
+                        tok = int(np.argmax(score))
+                    else:
+                        tok = int(np.argmax(yp))
+                else:
+                    tok = int(np.argmax(yp + _gumbel_row(_stream_key(seed, 2), V)))
+                ot[o], ol[o] = tok, yp[tok] - zp
+                break
+            ac[j] = a
+
+
+def spec_verify_sample(p_logits: torch.Tensor, q_logits: torch.Tensor, draft, p_row0, q_row0, d_off, ks, temps, seeds,
+                       out_row0=None, out_tok: Optional[torch.Tensor] = None, out_lp: Optional[torch.Tensor] = None):
+    """Speculative-sampling verification of nb blocks in one call. Block j: ks[j] >= 1 draft
+    tokens draft[d_off[j]:d_off[j] + k], target rows p_logits[p_row0[j]:p_row0[j] + k + 1],
+    draft rows q_logits[q_row0[j]:q_row0[j] + k], temperature temps[j] > 0 (host arrays of
+    length nb; blocks may share rows). seeds: one int64 per position, sum(k + 1) in block
+    order (host array). draft: int32 host array or tensor on the logits' device.
+    Writes, for i <= accepted[j], the emitted token and its log-probability under the
+    target at row out_row0[j] + i of out_tok / out_lp (default: positions in block order,
+    fresh tensors); rows after that are left alone. Returns (out_tok int32, out_lp fp32,
+    accepted int32 [nb]), on the logits' device; nothing is synchronised."""
+    import numpy as np
+    Rp, V = p_logits.shape
+    Rq = q_logits.shape[0]
+    if q_logits.shape[1] != V or q_logits.dtype != p_logits.dtype or q_logits.device != p_logits.device:
+        raise ValueError("spec_verify_sample: target and draft logits differ in width, dtype or device")
+    # (the row stride of a one-row matrix is never used and may be anything)
+    ps, qs = (t.stride(0) if t.shape[0] > 1 else V for t in (p_logits, q_logits))
+    if p_logits.stride(1) != 1 or q_logits.stride(1) != 1 or ps < V or qs < V:
+        raise ValueError("spec_verify_sample: a row stride is smaller than V")
+    dev = p_logits.device
+    host_draft = not isinstance(draft, torch.Tensor)
+    n_draft = len(draft) if host_draft else draft.numel()
+    nb = len(ks)
+    n_out = None if out_tok is None else min(out_tok.numel(), out_lp.numel())
+    p_row0, q_row0, d_off, ks, temps, lrow0, out_row0, Lp, Lq = _spec_blocks(
+        Rp, Rq, n_draft, (1 << 62) if n_out is None else n_out, V, p_row0, q_row0, d_off, ks, temps, out_row0)
+    if out_tok is None:
+        n_out = int((out_row0 + ks + 1).max()) if nb else 0
+        out_tok = torch.zeros(n_out, dtype=torch.int32, device=dev)
+        out_lp = torch.zeros(n_out, dtype=torch.float32, device=dev)
+    assert out_tok.dtype == torch.int32 and out_lp.dtype == torch.float32
+    assert out_tok.is_contiguous() and out_lp.is_contiguous()
+    accepted = torch.zeros(nb, dtype=torch.int32, device=dev)
+    seeds = np.asarray(seeds).astype(np.int64).reshape(-1)
+    if seeds.shape[0] != Lp:
+        raise ValueError("spec_verify_sample: one seed per position (sum of k + 1)")
+    if nb == 0:
+        return out_tok, out_lp, accepted
+    if not use_native(p_logits):
+        d = np.asarray(draft, np.int64) if host_draft else draft.numpy()
+        _spec_verify_ref(p_logits, q_logits, d, p_row0, q_row0, d_off, ks, temps, lrow0, out_row0, seeds, out_tok,
+                         out_lp, accepted)
+        return out_tok, out_lp, accepted
+    assert p_logits.dtype in (torch.bfloat16, torch.float32)
+    K = kernels()
+    BW = K.spec_block_words()
+    # one pinned staging, one H2D: seeds (int64) | blocks | row map | draft tokens
+    n_dr = n_draft if host_draft else 0
+    stage = torch.empty(2 * Lp + BW * nb + Lp + Lq + n_dr, dtype=torch.int32, pin_memory=True)
+    h = stage.numpy()
+    h[:2 * Lp].view(np.int64)[:] = seeds
+    blk = h[2 * Lp:2 * Lp + BW * nb].reshape(nb, BW)
+    blk[:, 0], blk[:, 1], blk[:, 2], blk[:, 3], blk[:, 4], blk[:, 5] = p_row0, q_row0, d_off, ks, lrow0, out_row0
+    blk[:, 6] = temps.view(np.int32)
+    blk[:, 7] = 0
+    o_map = 2 * Lp + BW * nb
+    idx = np.arange(nb, dtype=np.int32)
+    h[o_map:o_map + Lp] = np.repeat(idx, ks + 1)
+    h[o_map + Lp:o_map + Lp + Lq] = np.repeat(idx, ks)
+    if host_draft:
+        h[o_map + Lp + Lq:] = np.asarray(draft, np.int32)
+    d_stage = stage.to(dev, non_blocking=True)
+    if host_draft:
+        draft = d_stage[o_map + Lp + Lq:]
+    assert draft.dtype == torch.int32 and draft.is_contiguous() and draft.device == dev
+    need = K.spec_ws_bytes(Lp, Lq, V)
+    # scratch of the three launches, any content on entry; never part of a captured graph,
+    # so a grown one simply replaces the old (stream-ordered)
+    ws = _SPEC_WS.get((dev.type, dev.index))
+    if ws is None or ws.numel() < need:
+        ws = _SPEC_WS[(dev.type, dev.index)] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=dev)
+    base = d_stage.data_ptr()
+    K.spec_verify_sample(p_logits.data_ptr(), Rp, ps, q_logits.data_ptr(), Rq, qs,
+                         1 if p_logits.dtype == torch.float32 else 0, V, nb, blk.ctypes.data, base + 8 * Lp,
+                         base + 4 * o_map, base, draft.data_ptr(), n_draft, out_tok.data_ptr(), out_lp.data_ptr(),
+                         n_out, accepted.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out_tok, out_lp, accepted
 
 
 # ---------------------------------------------------------------------------

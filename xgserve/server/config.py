@@ -143,6 +143,8 @@ class SpecSection:
     draft_model: Optional[str] = None
     num_speculative_tokens: int = 0
     min_acceptance_rate: float = 0.5
+    # speculate sampled requests (temperature > 0, no top-p / top-k) by rejection sampling
+    sampled: bool = False
 
 
 @dataclass

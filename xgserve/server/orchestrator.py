@@ -752,7 +752,9 @@ class InferenceServer:
             sfs = [x["speedup_factor"] for x in specs if x.get("speedup_factor") is not None]
             self.metrics.set_spec_totals(sum(x["draft_tokens_proposed"] for x in specs),
                                          sum(x["draft_tokens_accepted"] for x in specs),
-                                         sum(sfs) / len(sfs) if sfs else None)
+                                         sum(sfs) / len(sfs) if sfs else None,
+                                         sum(x.get("sampled_draft_tokens_proposed", 0) for x in specs),
+                                         sum(x.get("sampled_draft_tokens_accepted", 0) for x in specs))
         for rid in list(self.routable):
             r = self.replicas.get(rid)
             if r is None:
