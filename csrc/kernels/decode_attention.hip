@@ -324,17 +324,39 @@ __device__ __forceinline__ float combine_splits(const float* __restrict__ lse, c
 // 3 = neither (launch + merge + store only); 4 = the kernel with cached (temporal) K/V loads.
 // SPRO (FQ): the split prologue (qkv_issue before the K/V preloads, qkv_finish
 // after; QKV plans with S <= 8 -- all of them today); false: the classic prologue.
-template <int D, int G, bool FQ, bool KL = false, int NB = 2, int PR = 0, bool SPRO = true>
-__global__ void __launch_bounds__(256) decode_attn_kernel(
+// The workgroup's LDS as one 16-B aligned buffer: byte offsets of its arrays. The K
+// tiles exist only with KL, the q rows only with FQ.
+template <int D, int G, bool FQ, bool KL>
+struct DecodeSmem {
+  static constexpr int W = DecodeCfg<D, G>::WAVES;
+  static constexpr int V = 0;                                   // uint16_t [W][16 * D]
+  static constexpr int K = V + W * 16 * D * 2;                  // uint16_t [W][16 * D]
+  static constexpr int O = K + (KL ? W * 16 * D * 2 : 0);       // float [W][G][D]
+  static constexpr int Q = O + W * G * D * 4;                   // uint16_t [G * D]
+  static constexpr int M = Q + (FQ ? G * D * 2 : 0);            // float [W][16]
+  static constexpr int L = M + W * 16 * 4;                      // float [W][16]
+  static constexpr int BYTES = L + W * 16 * 4;
+};
+
+// The workgroup's work as a device function of its logical block index (kv head,
+// sequence, key split), the index `tid` of the calling thread among the `nthreads`
+// (C::WAVES waves) that run it, and its DecodeSmem<>::BYTES of LDS: decode_attn_kernel
+// below is its launch, and mixed_attn_kernel (mixed_attention.hip) runs the unfused,
+// unsplit form in the trailing blocks of a grid shared with the prompt rows of the same
+// step. (The FQ prologues take thread and grid indices from the launch itself: FQ is
+// for the kernel below only.)
+template <int D, int G, bool FQ, bool KL, int NB, int PR, bool SPRO>
+__device__ __forceinline__ void decode_attn_body(
+    const int kvh, const int b, const int split, const int tid, const int nthreads, char* smem,
     const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* kc, const uint16_t* vc,
     const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ seq_lens,
     float* __restrict__ part_out, float* __restrict__ part_lse, uint16_t* __restrict__ out, int64_t out_stride,
-    int Hq, int Hkv, int bs, float scale, int num_splits, QkvFuse fq) {
+    int Hq, int Hkv, int bs, float scale, int num_splits, const QkvFuse fq) {
   using C = DecodeCfg<D, G>;
-  const int kvh = blockIdx.x, b = blockIdx.y, split = blockIdx.z;
+  using SM = DecodeSmem<D, G, FQ, KL>;
   // wid through readfirstlane: wave-uniform to the compiler, so the page-table reads of
   // load_tile are scalar loads (lgkmcnt) and do not wait behind the prologue's vector loads
-  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15;
   const int L = seq_lens[b];
   const int ntiles = (L + 15) >> 4;
@@ -343,11 +365,12 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(
   const int t_begin = split * tps;
   const int t_end = min(ntiles, t_begin + tps);
 
-  __shared__ __attribute__((aligned(16))) uint16_t v_lds[C::WAVES][16 * D];
-  __shared__ __attribute__((aligned(16))) uint16_t k_lds[KL ? C::WAVES : 1][KL ? 16 * D : 8];
-  __shared__ float m_lds[C::WAVES][16], l_lds[C::WAVES][16];
-  __shared__ float o_lds[C::WAVES][G][D];
-  __shared__ __attribute__((aligned(16))) uint16_t q_lds[FQ ? G * D : 8];
+  uint16_t(*v_lds)[16 * D] = reinterpret_cast<uint16_t(*)[16 * D]>(smem + SM::V);
+  uint16_t(*k_lds)[16 * D] = reinterpret_cast<uint16_t(*)[16 * D]>(smem + SM::K);
+  float(*m_lds)[16] = reinterpret_cast<float(*)[16]>(smem + SM::M);
+  float(*l_lds)[16] = reinterpret_cast<float(*)[16]>(smem + SM::L);
+  float(*o_lds)[G][D] = reinterpret_cast<float(*)[G][D]>(smem + SM::O);
+  uint16_t* q_lds = reinterpret_cast<uint16_t*>(smem + SM::Q);
 
   const int32_t* bt = block_tables + static_cast<int64_t>(b) * bt_stride;
   const int64_t head_stride = static_cast<int64_t>(bs) * D;
@@ -537,7 +560,7 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(
       for (int r = 0; r < 4; ++r) o_lds[wid][li][mt * 16 + 4 * g + r] = o[mt][r];
   }
   __syncthreads();
-  for (int idx = threadIdx.x; idx < G * D; idx += blockDim.x) {
+  for (int idx = tid; idx < G * D; idx += nthreads) {
     const int h = idx / D, d = idx % D;
     float M = -INFINITY;
 #pragma unroll
@@ -563,6 +586,20 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(
     }
   }
 }
+
+template <int D, int G, bool FQ, bool KL = false, int NB = 2, int PR = 0, bool SPRO = true>
+__global__ void __launch_bounds__(256) decode_attn_kernel(
+    const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* kc, const uint16_t* vc,
+    const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ seq_lens,
+    float* __restrict__ part_out, float* __restrict__ part_lse, uint16_t* __restrict__ out, int64_t out_stride,
+    int Hq, int Hkv, int bs, float scale, int num_splits, QkvFuse fq) {
+  __shared__ __attribute__((aligned(16))) char smem[DecodeSmem<D, G, FQ, KL>::BYTES];
+  decode_attn_body<D, G, FQ, KL, NB, PR, SPRO>(blockIdx.x, blockIdx.y, blockIdx.z, threadIdx.x, blockDim.x, smem, q,
+                                               q_stride, kc, vc, block_tables, bt_stride, seq_lens, part_out,
+                                               part_lse, out, out_stride, Hq, Hkv, bs, scale, num_splits, fq);
+}
+
+#ifndef XGK_ATTN_DEVICE_ONLY  // (mixed_attention.hip includes this file for the device code above)
 // Split-K reduction launch: out[b, h, :] = sum_s softmax(lse)_s * part_out[b, h, s, :]
 template <int D>
 __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restrict__ part_out,
@@ -673,5 +710,6 @@ int decode_attention_fq(const float* part, int S_qkv, const int32_t* positions, 
 #undef XGK_DECF
   return -1;
 }
+#endif  // XGK_ATTN_DEVICE_ONLY
 
 }  // namespace xgk

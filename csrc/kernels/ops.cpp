@@ -42,6 +42,9 @@ int decode_attention(const uint16_t*, int64_t, const uint16_t*, const uint16_t*,
                      float*, float*, uint16_t*, int64_t, int, int, int, int, int, float, int, hipStream_t);
 int prefill_attention(const uint16_t*, int64_t, const uint16_t*, const uint16_t*, const int32_t*, int, const int32_t*,
                       const int32_t*, uint16_t*, int64_t, int, int, int, int, int, int, float, hipStream_t, int);
+int mixed_attention(uint16_t*, int64_t, const int32_t*, const float*, uint16_t*, uint16_t*, const int32_t*, int, int,
+                    const int32_t*, int, const int32_t*, const int32_t*, int, const int32_t*, const int32_t*, int, int,
+                    uint16_t*, int64_t, int, int, int, int, float, int, hipStream_t);
 void argmax_logprob(const void*, int, int64_t, int, int, int32_t*, float*, hipStream_t, float* ws = nullptr,
                     int* cnt = nullptr);
 int argmax_ws_floats_per_row();
@@ -214,6 +217,21 @@ PYBIND11_MODULE(_kernels, m) {
   }, py::arg("q"), py::arg("qs"), py::arg("kc"), py::arg("vc"), py::arg("bt"), py::arg("bts"), py::arg("qsl"),
      py::arg("sl"), py::arg("out"), py::arg("os"), py::arg("ns"), py::arg("maxq"), py::arg("Hq"), py::arg("Hkv"),
      py::arg("D"), py::arg("bs"), py::arg("scale"), py::arg("st"), py::arg("gh") = 0);
+  // a mixed step's attention: rope_cache over the T rows of qkv, then the decode rows [0, nd) and the
+  // prompt rows [nd, T) in one launch (mixed_attention.hip). Refuses, with nothing enqueued, what the
+  // fused launch does not cover; the caller then makes the three separate calls
+  m.def("mixed_attention", [](uintptr_t qkv, int64_t row_stride, uintptr_t pos, uintptr_t cs, uintptr_t kc,
+                              uintptr_t vc, uintptr_t slots, int T, int nd, uintptr_t dec_bt, int dec_bts,
+                              uintptr_t dec_sl, uintptr_t pre_bt, int pre_bts, uintptr_t pre_qsl, uintptr_t pre_sl,
+                              int num_pre, int maxq, uintptr_t out, int64_t os, int Hq, int Hkv, int D, int bs,
+                              float scale, int apply_rope, uintptr_t st) {
+    check(xgk::mixed_attention(P<uint16_t>(qkv), row_stride, P<const int32_t>(pos), P<const float>(cs),
+                               P<uint16_t>(kc), P<uint16_t>(vc), P<const int32_t>(slots), T, nd,
+                               P<const int32_t>(dec_bt), dec_bts, P<const int32_t>(dec_sl), P<const int32_t>(pre_bt),
+                               pre_bts, P<const int32_t>(pre_qsl), P<const int32_t>(pre_sl), num_pre, maxq,
+                               P<uint16_t>(out), os, Hq, Hkv, D, bs, scale, apply_rope, S(st)),
+          "mixed_attention");
+  });
   // ws / cnt (optional): the split-row form -- B x argmax_ws_floats_per_row() floats and B zeroed
   // ints (re-armed by every launch)
   m.def("argmax_logprob", [](uintptr_t logits, int is_f32, int64_t stride, int B, int V, uintptr_t tok, uintptr_t lp,

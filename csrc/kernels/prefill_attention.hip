@@ -321,15 +321,18 @@ __device__ __forceinline__ float fast_exp2(float x) {
 #endif
 }
 
+// The workgroup's work as a device function of its logical block index `bid` (see the
+// grid order above) and its NSLOT * SLOT bytes of 16-B aligned LDS: prefill_attn2_kernel
+// below is its launch, and mixed_attn_kernel (mixed_attention.hip) runs it in the
+// leading blocks of a grid shared with the decode rows of the same step.
 template <int NW, int GH, int KS, int NSLOT>
-__global__ void __launch_bounds__(64 * NW, (NW == 4 && NSLOT <= 2 ? 2 : 1)) prefill_attn2_kernel(
-    const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* __restrict__ kc,
+__device__ __forceinline__ void prefill_attn2_body(
+    const int bid, char* lds, const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* __restrict__ kc,
     const uint16_t* __restrict__ vc, const int32_t* __restrict__ block_tables, int bt_stride,
     const int32_t* __restrict__ qsl, const int32_t* __restrict__ seq_lens, uint16_t* __restrict__ out,
     int64_t out_stride, int num_seqs, int Hq, int Hkv, int bs, float scale_log2, int tiles_per_seq, int n_hg) {
   using C = Pf2Cfg<NW, GH, KS, NSLOT>;
   constexpr int D = C::D;
-  const int bid = blockIdx.x;
   const int hg = bid % n_hg;
   const int rest = bid / n_hg;
   const int s = rest % num_seqs;
@@ -346,8 +349,6 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 && NSLOT <= 2 ? 2 : 1)) pref
   const int h = hg * GH + hh;
   const int kvh = (hg * GH) / (Hq / Hkv);
   const int r = lane & 31, hf = lane >> 5;
-
-  __shared__ __attribute__((aligned(16))) char lds[NSLOT * C::SLOT];
 
   // Q^T (B operand of S^T): lane holds Q[row r][16 ks + 8 hf + 0..7]
   const int my_row = i0 + rb * 32 + r;
@@ -569,6 +570,34 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 && NSLOT <= 2 ? 2 : 1)) pref
   }
 }
 
+template <int NW, int GH, int KS, int NSLOT>
+__global__ void __launch_bounds__(64 * NW, (NW == 4 && NSLOT <= 2 ? 2 : 1)) prefill_attn2_kernel(
+    const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* __restrict__ kc,
+    const uint16_t* __restrict__ vc, const int32_t* __restrict__ block_tables, int bt_stride,
+    const int32_t* __restrict__ qsl, const int32_t* __restrict__ seq_lens, uint16_t* __restrict__ out,
+    int64_t out_stride, int num_seqs, int Hq, int Hkv, int bs, float scale_log2, int tiles_per_seq, int n_hg) {
+  __shared__ __attribute__((aligned(16))) char lds[NSLOT * Pf2Cfg<NW, GH, KS, NSLOT>::SLOT];
+  prefill_attn2_body<NW, GH, KS, NSLOT>(blockIdx.x, lds, q, q_stride, kc, vc, block_tables, bt_stride, qsl, seq_lens,
+                                        out, out_stride, num_seqs, Hq, Hkv, bs, scale_log2, tiles_per_seq, n_hg);
+}
+
+// The configuration prefill_attention picks by itself (gh == 0) for a D = 128 launch:
+// waves, heads per workgroup, key phases, ring slots.
+struct Pf2Choice {
+  int nw, gh, ks, ns;
+};
+inline Pf2Choice pf2_default(int num_seqs, int max_q_len, int Hq, int G) {
+  const int ghh = G % 2 == 0 ? 2 : 1;
+  // 8 waves: 128 rows x 2 heads once that still gives two workgroups per CU; else
+  // 64 rows x 2 heads x 2 key phases (short prompts: half the serial tile chain).
+  // profiles/r3_prefill_attn2.md: 8K 882 / 2K 598 / 512 17 us (8B heads)
+  const int64_t wg8 = static_cast<int64_t>(num_seqs) * ((max_q_len + 32 * (8 / ghh) - 1) / (32 * (8 / ghh))) *
+                      (Hq / ghh);
+  const int ks = wg8 >= 512 ? 1 : 2;
+  return {8, ghh, ks, ks == 2 ? 2 : 3};
+}
+
+#ifndef XGK_ATTN_DEVICE_ONLY  // (mixed_attention.hip includes this file for the device code above)
 // GQA grouping: GH query heads of one kv head per workgroup (4*GH waves). gh <= 0
 // picks the widest GH in {4, 2, 1} dividing the group size that still gives >= 256
 // workgroups (one per CU); measured (bench/prefill_bench.py, profiles/
@@ -592,14 +621,8 @@ int prefill_attention(const uint16_t* q, int64_t q_stride, const uint16_t* kc, c
       nw = ((-gh) / 10) % 10;
       ghh = (-gh) % 10;
     } else {
-      ghh = G % 2 == 0 ? 2 : 1;
-      // 8 waves: 128 rows x 2 heads once that still gives two workgroups per CU; else
-      // 64 rows x 2 heads x 2 key phases (short prompts: half the serial tile chain).
-      // profiles/r3_prefill_attn2.md: 8K 882 / 2K 598 / 512 17 us (8B heads)
-      const int64_t wg8 = static_cast<int64_t>(num_seqs) * ((max_q_len + 32 * (8 / ghh) - 1) / (32 * (8 / ghh))) *
-                          (Hq / ghh);
-      nw = 8;
-      ks = wg8 >= 512 ? 1 : 2;
+      const Pf2Choice c = pf2_default(num_seqs, max_q_len, Hq, G);
+      nw = c.nw, ghh = c.gh, ks = c.ks, ns = c.ns;
     }
     if (ns == 0) ns = ks == 2 ? 2 : (nw == 8 ? 3 : 2);
     if (G % ghh != 0 || nw % (ghh * ks) != 0) return -1;
@@ -657,5 +680,6 @@ int prefill_attention(const uint16_t* q, int64_t q_stride, const uint16_t* kc, c
 #undef XGK_PF
   return -1;
 }
+#endif  // XGK_ATTN_DEVICE_ONLY
 
 }  // namespace xgk

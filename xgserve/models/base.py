@@ -9,6 +9,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .. import ops
+from ..ops import attention
 from ..ops.attention import DecodeWorkspace
 from ..parallel.state import get_state
 
@@ -68,6 +69,18 @@ class PagedAttention:
                  cos_sin: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         T = qkv.shape[0]
         kc, vc = kv
+        nd = meta.num_decodes
+        # a mixed step (decode rows and prompt rows): one native call, rope_cache + ONE attention
+        # launch (XGS_TUNE mixed_attn; every other step, and layouts it does not cover, below).
+        # Only this entry, QKV as a tensor, has the fused form: mixed steps whose QKV arrives as
+        # split-K partials (from_partials) keep rope_cache_partials and the two attention launches
+        if attention.MIXED_ATTN and ops.mixed_attention_ok(qkv, nd, meta.num_splits, self.Hq, self.Hkv, self.D):
+            if out is None:
+                out = torch.empty(T, self.Hq, self.D, dtype=qkv.dtype, device=qkv.device)
+            ops.mixed_attention(qkv, meta.positions, cos_sin, kc, vc, meta.slot_mapping, nd, meta.dec_block_tables,
+                                meta.dec_seq_lens, meta.pre_block_tables, meta.pre_qsl, meta.pre_seq_lens,
+                                meta.pre_max_q, self.Hq, self.Hkv, self.D, self.scale, self.use_rope, out=out)
+            return out.view(T, self.Hq * self.D)
         ops.rope_cache(qkv, meta.positions, cos_sin, kc, vc, meta.slot_mapping, self.Hq, self.Hkv, self.D,
                        self.use_rope)
         q = qkv[:, :self.Hq * self.D].view(T, self.Hq, self.D)
@@ -98,7 +111,8 @@ class PagedAttention:
             out = torch.empty(T, self.Hq, self.D, dtype=q.dtype, device=q.device)
         nd = meta.num_decodes
         # (decode rows' attention on a side stream under the prefill chunk's attention
-        # measured within noise, profiles/r2_mixed_attn_overlap.md)
+        # measured within noise, profiles/r2_mixed_attn_overlap.md; both in one launch:
+        # __call__ and profiles/mixed_attn.md)
         if nd > 0:
             ops.decode_attention(q[:nd], kc, vc, meta.dec_block_tables, meta.dec_seq_lens, self.scale,
                                  meta.num_splits, meta.workspace, out=out[:nd])

@@ -10,7 +10,7 @@ from .rope import RotaryCache, rope_cache, rope_cache_ref, build_cos_sin, rope_c
 from . import linear
 from .linear import skinny_linear, PendingSum
 from .attention import (decode_attention, decode_attention_fused, prefill_attention, decode_attention_ref,
-                        prefill_attention_ref, choose_num_splits)
+                        prefill_attention_ref, choose_num_splits, mixed_attention, mixed_attention_ok)
 from .sampling import argmax_logprob, sample_tokens, argmax_logprob_ref, segment_sum, subst_tokens
 from .sampling import top_logprobs, top_logprobs_ref, TOPLP_MAX
 from .sampling import spec_verify_sample
@@ -26,6 +26,7 @@ __all__ = [
     "silu_and_mul", "gelu_tanh", "silu_and_mul_ref", "gelu_tanh_ref",
     "RotaryCache", "rope_cache", "rope_cache_ref", "build_cos_sin",
     "decode_attention", "decode_attention_fused", "prefill_attention", "decode_attention_ref", "prefill_attention_ref", "choose_num_splits",
+    "mixed_attention", "mixed_attention_ok",
     "argmax_logprob", "sample_tokens", "argmax_logprob_ref", "segment_sum", "subst_tokens",
     "spec_verify_sample",
     "process_logits", "process_scratch", "logit_state_alloc", "logit_state_cells", "logit_state_reset",

@@ -149,6 +149,51 @@ def decode_attention_fused(pend, positions: torch.Tensor, slot_mapping: torch.Te
     return out
 
 
+# a mixed step's attention as rope_cache + ONE launch for the decode and the prompt rows
+# (csrc/kernels/mixed_attention.hip). XGS_TUNE mixed_attn=0: three launches (rope_cache,
+# decode_attention, prefill_attention). +1.7 % tokens/s at 64 concurrent: profiles/mixed_attn.md
+MIXED_ATTN = __import__("xgserve.tune", fromlist=["get_bool"]).get_bool("mixed_attn", True)
+MIXED_ATTN_GROUPS = (1, 2, 4, 8)
+
+
+def mixed_attention_ok(qkv: torch.Tensor, num_decodes: int, num_splits: int, Hq: int, Hkv: int, D: int) -> bool:
+    """The layouts mixed_attention covers: a GPU step with decode rows AND prompt rows,
+    unsplit decode attention, D = 128 and a GQA group of 1 / 2 / 4 / 8."""
+    return (use_native(qkv) and 0 < num_decodes < qkv.shape[0] and num_splits == 1 and D == 128
+            and Hq % Hkv == 0 and Hq // Hkv in MIXED_ATTN_GROUPS)
+
+
+def mixed_attention(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
+                    v_cache: torch.Tensor, slot_mapping: torch.Tensor, num_decodes: int,
+                    dec_block_tables: torch.Tensor, dec_seq_lens: torch.Tensor, pre_block_tables: torch.Tensor,
+                    pre_qsl: torch.Tensor, pre_seq_lens: torch.Tensor, max_q_len: int, Hq: int, Hkv: int, D: int,
+                    scale: float, apply_rope: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RoPE + KV append of all T rows of qkv [T, >= (Hq + 2 Hkv) D] (rope_cache, in place),
+    then the attention of the decode rows [0, num_decodes) and of the prompt chunks in rows
+    [num_decodes, T) in one launch -> out [T, Hq, D]. Every row is what rope_cache +
+    decode_attention (num_splits = 1) + prefill_attention give, bit for bit. The native
+    entry raises for what it does not cover (mixed_attention_ok)."""
+    T = qkv.shape[0]
+    assert qkv.stride(-1) == 1 and positions.dtype == torch.int32 and slot_mapping.dtype == torch.int32
+    assert cos_sin.dtype == torch.float32 and k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert qkv.shape[1] >= (Hq + 2 * Hkv) * D and qkv.dtype == torch.bfloat16
+    for t in (dec_block_tables, dec_seq_lens, pre_block_tables, pre_qsl, pre_seq_lens):
+        assert t.dtype == torch.int32
+    assert dec_block_tables.stride(1) == 1 and pre_block_tables.stride(1) == 1
+    assert dec_seq_lens.shape[0] >= num_decodes and dec_block_tables.shape[0] >= num_decodes
+    if out is None:
+        out = torch.empty(T, Hq, D, dtype=qkv.dtype, device=qkv.device)
+    assert out.shape[0] == T and out.stride(-1) == 1
+    kernels().mixed_attention(qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), cos_sin.data_ptr(),
+                              k_cache.data_ptr(), v_cache.data_ptr(), slot_mapping.data_ptr(), T, int(num_decodes),
+                              dec_block_tables.data_ptr(), dec_block_tables.stride(0), dec_seq_lens.data_ptr(),
+                              pre_block_tables.data_ptr(), pre_block_tables.stride(0), pre_qsl.data_ptr(),
+                              pre_seq_lens.data_ptr(), pre_seq_lens.shape[0], int(max_q_len), out.data_ptr(),
+                              out.stride(0), Hq, Hkv, D, k_cache.shape[2], float(scale), 1 if apply_rope else 0,
+                              stream_ptr())
+    return out
+
+
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
                       query_start_loc: torch.Tensor, seq_lens: torch.Tensor, max_q_len: int, scale: float,
                       out: Optional[torch.Tensor] = None, gh: Optional[int] = None) -> torch.Tensor:

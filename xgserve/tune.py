@@ -21,6 +21,9 @@ Keys (default in brackets; every default is the production setting):
   resid_inlaunch_kb [32]   in-launch residual reduce bound of the fused decode GEMMs
   decode_depth [2]         decode attention K/V register pipeline depth (4: depth 2 with the classic QKV prologue)
   decode_max_splits [16]   split-K cap of decode attention
+  mixed_attn [1]           mixed steps whose QKV is a tensor (library QKV GEMM, e.g. 63 rows + a 512-token prompt):
+                           the decode and the prompt rows' attention in one launch (0: three launches). Steps
+                           whose QKV arrives as split-K partials keep rope_cache_partials + two launches
   gemm_ar [1]              TP decode: all-reduce inside the row-parallel O / down GEMM launches
   gemm_ar_shared [0]       test-only: GG_AR also for <= 4 ranks sharing one GPU (one-GPU boxes)
   small_m_tiles [128]      column-tile statistics a M <= 16 consumer combines (64: pair combine above)
@@ -37,7 +40,7 @@ import os
 from typing import Dict
 
 KEYS = {"fused_decode", "async_sched", "early_release", "spin_wait", "pf", "pf_windows", "moe_pf", "moe_w2_small", "argmax_split", "gemm_ar", "gemm_ar_shared", "small_m_tiles", "krot", "m64_plans", "mw_plans",
-        "mw_max_tokens", "resid_inlaunch_kb", "decode_depth", "decode_max_splits", "ar_ll_max", "sim_ar_us",
+        "mw_max_tokens", "resid_inlaunch_kb", "decode_depth", "decode_max_splits", "mixed_attn", "ar_ll_max", "sim_ar_us",
         "tp_overlap_chunks", "tp_overlap_min_tokens", "ep_exact_min_pairs"}
 
 
