@@ -4,6 +4,8 @@ step's sampler alone costs on the same target rows.
   64 blocks, k = 4, V = 128256, bf16: 320 target rows + 256 draft rows.
   A: ops.spec_verify_sample (three launches + one small H2D of the block descriptors)
   B: ops.sample_tokens on the 320 target rows (what a verify step spends sampling anyway)
+With --top-p / --top-k every block is truncated: the draft draws with them, A runs the six
+launches of the truncated form and B samples with them too.
 
 Device events around windows of `--iters` back-to-back calls, after a warm-up of every
 shape; the two are alternated window by window inside one process and the median and the
@@ -34,6 +36,8 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("spec_sample_bench: needs a GPU")
@@ -50,16 +54,25 @@ def main():
     seeds = np.arange(1, Lp + 1, dtype=np.int64) * 7919
     p_row0, q_row0 = np.arange(nb) * (k + 1), np.arange(nb) * k
     qt = torch.from_numpy(np.repeat(temps, k)).to(dev)
-    draft, _ = ops.sample_tokens(q, qt, None, None, torch.from_numpy(seeds[:Lq].copy()).to(dev), step=0)
+    trunc = a.top_p < 1.0 or a.top_k > 0
+    tkw = dict(top_ps=np.full(nb, a.top_p, np.float32), top_ks=np.full(nb, a.top_k, np.int32)) if trunc else {}
+
+    def rows_of(n):  # per-row top_p / top_k tensors for ops.sample_tokens
+        if not trunc:
+            return None, None
+        return (torch.full((n,), a.top_p, dtype=torch.float32, device=dev),
+                torch.full((n,), a.top_k, dtype=torch.int32, device=dev))
+
+    draft, _ = ops.sample_tokens(q, qt, *rows_of(Lq), torch.from_numpy(seeds[:Lq].copy()).to(dev), step=0)
     draft = draft.contiguous()
     pt = torch.from_numpy(np.repeat(temps, k + 1)).to(dev)
     pseeds = torch.from_numpy(seeds).to(dev)
 
     def run_a():
-        return ops.spec_verify_sample(p, q, draft, p_row0, q_row0, q_row0, ks, temps, seeds)
+        return ops.spec_verify_sample(p, q, draft, p_row0, q_row0, q_row0, ks, temps, seeds, **tkw)
 
     def run_b():
-        return ops.sample_tokens(p, pt, None, None, pseeds, step=0)
+        return ops.sample_tokens(p, pt, *rows_of(Lp), pseeds, step=0)
 
     for _ in range(a.warmup):
         run_a()
@@ -85,6 +98,7 @@ def main():
     esz = p.element_size()
     read = (Lp + Lq) * V * esz + (Lp + Lq) * V * esz  # stats pass + draw pass
     res = {"bench": "spec_verify_sample", "blocks": nb, "k": k, "vocab": V, "dtype": "bf16",
+           "top_p": a.top_p, "top_k": a.top_k,
            "spec_verify_ms_median": round(statistics.median(ta), 4), "spec_verify_ms_min": round(min(ta), 4),
            "spec_verify_ms_max": round(max(ta), 4),
            "sample_tokens_ms_median": round(statistics.median(tb), 4), "sample_tokens_ms_min": round(min(tb), 4),

@@ -51,12 +51,13 @@ int argmax_ws_floats_per_row();
 void sample_tokens(const void*, int, int64_t, int, int, const float*, const float*, const int32_t*, const uint64_t*,
                    uint64_t, int32_t*, float*, void*, hipStream_t);
 size_t sample_ws_row_bytes();
-void spec_verify_sample(const void*, int64_t, const void*, int64_t, int, int, int, int, int, const void*,
+void spec_verify_sample(const void*, int64_t, const void*, int64_t, int, int, int, int, int, int, const void*,
                         const int32_t*, const uint64_t*, const int32_t*, int32_t*, float*, int32_t*, void*,
                         hipStream_t);
 int spec_block_words();
 int spec_parts(int, int);
-size_t spec_ws_bytes(int, int, int);
+size_t spec_ws_bytes(int, int, int, int);
+size_t spec_trow_bytes();
 int top_logprobs(const void*, int, int64_t, int, int, const int32_t*, int, const float*, int, int32_t*, float*, void*,
                  int*, hipStream_t);
 int top_logprobs_max();
@@ -256,9 +257,10 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("sample_ws_row_bytes", []() { return static_cast<int64_t>(xgk::sample_ws_row_bytes()); });
   // Speculative-sampling verification (spec_sample.hip). blk_host: the nb block
   // descriptors on the HOST (int32 [nb, spec_block_words()]: p_row0, q_row0, d_off, k,
-  // lrow0, out_row0, temperature bits, 0), checked here against the sizes of every array
-  // the kernels index with them; blk: their device copy; rmap: device int32, the block of
-  // each logical target row and then of each logical draft row; seeds: [sum (k + 1)].
+  // lrow0, out_row0, temperature bits, top_k, top_p bits, trow0), checked here against the
+  // sizes of every array the kernels index with them; blk: their device copy; rmap: device
+  // int32, the block of each logical target row and then of each logical draft row; seeds:
+  // [sum (k + 1)].
   m.def("spec_verify_sample", [](uintptr_t p_logits, int p_rows, int64_t p_stride, uintptr_t q_logits, int q_rows,
                                  int64_t q_stride, int is_f32, int V, int nb, uintptr_t blk_host, uintptr_t blk,
                                  uintptr_t rmap, uintptr_t seeds, uintptr_t draft, int n_draft, uintptr_t out_tok,
@@ -276,11 +278,12 @@ PYBIND11_MODULE(_kernels, m) {
     if (ws % 16) bad("workspace is not 16-byte aligned");
     const int32_t* b = P<const int32_t>(blk_host);
     const int BW = xgk::spec_block_words();
-    int64_t Lp = 0, Lq = 0;
+    int64_t Lp = 0, Lq = 0, nT = 0;  // nT: truncated logical rows (2 k + 1 per truncated block)
     for (int j = 0; j < nb; ++j, b += BW) {
       const int64_t k = b[3];
-      float t;
+      float t, tp;
       std::memcpy(&t, b + 6, 4);
+      std::memcpy(&tp, b + 8, 4);
       if (k < 1) bad("block " + std::to_string(j) + " has k < 1");
       if (!(t > 0.f) || !(t < 3.0e38f)) bad("block " + std::to_string(j) + " has no positive finite temperature");
       if (b[0] < 0 || b[0] + k + 1 > p_rows) bad("block " + std::to_string(j) + " leaves the target rows");
@@ -288,14 +291,22 @@ PYBIND11_MODULE(_kernels, m) {
       if (b[2] < 0 || b[2] + k > n_draft) bad("block " + std::to_string(j) + " leaves the draft tokens");
       if (b[4] != Lp) bad("block " + std::to_string(j) + ": lrow0 is not the running sum of k + 1");
       if (b[5] < 0 || b[5] + k + 1 > n_out) bad("block " + std::to_string(j) + " leaves the output rows");
+      if (!(tp > 0.f) || !(tp <= 1.f)) bad("block " + std::to_string(j) + " has top_p outside (0, 1]");
+      if (b[7] < 0) bad("block " + std::to_string(j) + " has a negative top_k");
+      if (tp < 1.f || (b[7] > 0 && b[7] < V)) {  // truncated: its scratch rows follow the earlier blocks'
+        if (b[9] != nT) bad("block " + std::to_string(j) + ": trow0 is not the running sum of 2 k + 1");
+        nT += 2 * k + 1;
+      }
       Lp += k + 1;
       Lq += k;
       if (Lp > 65535) bad("more than 65535 target rows");
     }
-    if (ws_bytes < static_cast<int64_t>(xgk::spec_ws_bytes(static_cast<int>(Lp), static_cast<int>(Lq), V)))
+    if (ws_bytes < static_cast<int64_t>(xgk::spec_ws_bytes(static_cast<int>(Lp), static_cast<int>(Lq), V,
+                                                           static_cast<int>(nT))))
       bad("workspace too small");
     xgk::spec_verify_sample(P<const void>(p_logits), p_stride, P<const void>(q_logits), q_stride, is_f32, V, nb,
-                            static_cast<int>(Lp), static_cast<int>(Lq), P<const void>(blk), P<const int32_t>(rmap),
+                            static_cast<int>(Lp), static_cast<int>(Lq), static_cast<int>(nT), P<const void>(blk),
+                            P<const int32_t>(rmap),
                             P<const uint64_t>(seeds), P<const int32_t>(draft), P<int32_t>(out_tok), P<float>(out_lp),
                             P<int32_t>(accepted), P<void>(ws), S(st));
     check(0, "spec_verify_sample");
@@ -305,7 +316,11 @@ PYBIND11_MODULE(_kernels, m) {
      py::arg("n_out"), py::arg("accepted"), py::arg("ws"), py::arg("ws_bytes"), py::arg("st"));
   m.def("spec_block_words", &xgk::spec_block_words);
   m.def("spec_parts", &xgk::spec_parts);
-  m.def("spec_ws_bytes", [](int Lp, int Lq, int V) { return static_cast<int64_t>(xgk::spec_ws_bytes(Lp, Lq, V)); });
+  // trunc_rows: sum of 2 k + 1 over the truncated blocks (each such row owns spec_trow_bytes() of scratch)
+  m.def("spec_ws_bytes", [](int Lp, int Lq, int V, int trunc_rows) {
+    return static_cast<int64_t>(xgk::spec_ws_bytes(Lp, Lq, V, trunc_rows));
+  }, py::arg("Lp"), py::arg("Lq"), py::arg("V"), py::arg("trunc_rows") = 0);
+  m.def("spec_trow_bytes", []() { return static_cast<int64_t>(xgk::spec_trow_bytes()); });
   // top-K tokens and log-probabilities of the asked rows (top_logprobs.hip). rows: int32 [n]
   // logits-row indices (0: rows 0..n-1); temps: fp32 indexed by logits row; ws / tickets
   // (optional): the split-row form -- n x top_logprobs_ws_words() u64 and n zeroed ints

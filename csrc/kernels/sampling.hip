@@ -9,7 +9,7 @@
 //     (<= 24 passes), no sort;
 //   * the draw is Gumbel-max: argmax(logit/T - log(-log u)), u from a
 //     per-(seed, step, row, index) counter hash, so a fixed seed reproduces.
-#include "samp_common.h"  // hash32, VecW, scalar_at: shared with spec_sample.hip
+#include "samp_common.h"  // hash32, VecW, scalar_at, the split-row geometry: shared with spec_sample.hip
 
 namespace xgk {
 
@@ -235,13 +235,10 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
 // whose cumulative count stays <= k; the row's argmax always. The draw is the v1
 // kernel's (same counter hash per (seed, step, index)). Each pass re-reads its chunk
 // (L2-resident after K1) with batched loads.
+// The geometry (samp::NT, NB, PMAX, RANGE, FIX), samp_bin, the kept-set rule samp_kept,
+// samp_scan and samp_ticket live in samp_common.h: the truncated verify kernels of
+// spec_sample.hip find the same kept sets with them.
 namespace samp {
-constexpr int NT = 256;       // threads per workgroup
-constexpr int NB = 1024;      // bins per histogram level
-constexpr int PMAX = 64;      // workgroups per row
-constexpr float RANGE = 40.f; // u beyond this is never kept by top-p / top-k
-constexpr float FIX = 1099511627776.f;  // 2^40: fixed-point probability mass
-
 // per-row workspace (bytes), zero before the first launch; every ticket winner
 // re-zeroes what it consumed, so each call leaves it zero
 struct Row {
@@ -388,99 +385,6 @@ __global__ void __launch_bounds__(samp::NT) samp_stats_kernel(const T* __restric
   }
 }
 
-// Row ticket (see gemm_m64g.hip agent_ticket): drain, one relaxed agent-scope add;
-// the winner acquires before reading what the other workgroups published.
-__device__ __forceinline__ bool samp_ticket(int* cnt, int last_value) {
-  __shared__ int flag;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int prev = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == last_value;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    flag = last;
-  }
-  __syncthreads();
-  return flag != 0;
-}
-
-// First bin (in order) where base + cumulative mass reaches `target` (or NB) and first
-// bin where base + cumulative count exceeds `kmax` (or NB), with the exclusive prefix
-// at those bins. Run by a whole workgroup over global histograms h_m / h_c, which it
-// re-zeroes.
-__device__ void samp_scan(unsigned long long* h_m, unsigned int* h_c, bool do_p, unsigned long long target,
-                          bool do_k, long long kmax, int& bin_p, unsigned long long& before_p, int& bin_k,
-                          long long& before_k) {
-  constexpr int PER = samp::NB / samp::NT;
-  __shared__ unsigned long long sm[samp::NT];
-  __shared__ long long sc[samp::NT];
-  __shared__ int best_p, best_k;
-  const int t = threadIdx.x;
-  unsigned long long lm[PER];
-  unsigned int lc[PER];
-  unsigned long long tm = 0;
-  long long tc = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    lm[j] = do_p ? __hip_atomic_load(h_m + t * PER + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-    lc[j] = do_k ? __hip_atomic_load(h_c + t * PER + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    tm += lm[j];
-    tc += lc[j];
-  }
-  if (t == 0) { best_p = samp::NB; best_k = samp::NB; }
-  sm[t] = tm;
-  sc[t] = tc;
-  __syncthreads();
-  for (int o = 1; o < samp::NT; o <<= 1) {  // inclusive Hillis-Steele scan
-    const unsigned long long am = t >= o ? sm[t - o] : 0ull;
-    const long long ac = t >= o ? sc[t - o] : 0ll;
-    __syncthreads();
-    sm[t] += am;
-    sc[t] += ac;
-    __syncthreads();
-  }
-  unsigned long long cm = sm[t] - tm;  // exclusive
-  long long cc = sc[t] - tc;
-  int fp = samp::NB, fk = samp::NB;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    if (fp == samp::NB && cm + lm[j] >= target) fp = t * PER + j;
-    if (fk == samp::NB && cc + lc[j] > kmax) fk = t * PER + j;
-    if (fp == samp::NB) cm += lm[j];
-    if (fk == samp::NB) cc += lc[j];
-  }
-  if (do_p && fp < samp::NB) atomicMin(&best_p, fp);
-  if (do_k && fk < samp::NB) atomicMin(&best_k, fk);
-  __syncthreads();
-  bin_p = best_p;
-  bin_k = best_k;
-  // the owners of the boundary bins publish the exclusive prefixes
-  __shared__ unsigned long long bp_before;
-  __shared__ long long bk_before;
-  if (do_p && fp == best_p && fp < samp::NB) bp_before = cm;
-  if (do_k && fk == best_k && fk < samp::NB) bk_before = cc;
-  __syncthreads();
-  before_p = bin_p < samp::NB ? bp_before : 0ull;
-  before_k = bin_k < samp::NB ? bk_before : 0ll;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    if (do_p) h_m[t * PER + j] = 0ull;
-    if (do_k) h_c[t * PER + j] = 0u;
-  }
-}
-
-// level-1 bin of u = M - y (>= NB: outside the range) and the sub-bin within it
-__device__ __forceinline__ int samp_bin(float u, int& sub) {
-  const float tt = u * (samp::NB / samp::RANGE);
-  const int b = tt < static_cast<float>(samp::NB) ? static_cast<int>(tt) : samp::NB;
-  sub = min(samp::NB - 1, max(0, static_cast<int>((tt - static_cast<float>(b)) * samp::NB)));
-  return b;
-}
-
 template <typename T, int LEVEL>
 __global__ void __launch_bounds__(samp::NT) samp_hist_kernel(const T* __restrict__ logits, int64_t stride, int V,
                                                             const float* __restrict__ temps,
@@ -490,57 +394,12 @@ __global__ void __launch_bounds__(samp::NT) samp_hist_kernel(const T* __restrict
   const SampParams q = samp_params(b, V, temps, top_ps, top_ks);
   samp::Row& r = ws[b];
   if (!q.use_p && !q.use_k) return;  // uniform per row: no workgroup of it takes a ticket
-  const bool do_p = q.use_p && (LEVEL == 1 || r.bp < samp::NB);
-  const bool do_k = q.use_k && (LEVEL == 1 || r.bk < samp::NB);
-  if (!do_p && !do_k) return;
-  const int bp = LEVEL == 2 ? r.bp : 0, bk = LEVEL == 2 ? r.bk : 0;
-  float M, logZ;
-  samp_row_stats(r, P, M, logZ);
-  __shared__ unsigned long long hm[samp::NB];
-  __shared__ unsigned int hc[samp::NB];
-  for (int i = threadIdx.x; i < samp::NB; i += samp::NT) { hm[i] = 0ull; hc[i] = 0u; }
-  __syncthreads();
   SampRow<T> sr{logits + b * stride, 0, 0};
   samp_chunk(V, P, p, sr.lo, sr.hi);
-  sr.visit([&](int, float x) {
-    const float y = scaled_logit(x, q.it);
-    int sub;
-    const int bin = samp_bin(M - y, sub);
-    if (bin >= samp::NB) return;
-    if (LEVEL == 1) {
-      if (do_p) atomicAdd(&hm[bin], static_cast<unsigned long long>(__expf(y - logZ) * samp::FIX));
-      if (do_k) atomicAdd(&hc[bin], 1u);
-    } else {
-      if (do_p && bin == bp) atomicAdd(&hm[sub], static_cast<unsigned long long>(__expf(y - logZ) * samp::FIX));
-      if (do_k && bin == bk) atomicAdd(&hc[sub], 1u);
-    }
-  });
-  __syncthreads();
-  unsigned long long* gm = LEVEL == 1 ? r.h1m : r.h2m;
-  unsigned int* gc = LEVEL == 1 ? r.h1c : r.h2c;
-  for (int i = threadIdx.x; i < samp::NB; i += samp::NT) {
-    if (do_p && hm[i]) atomicAdd(gm + i, hm[i]);
-    if (do_k && hc[i]) atomicAdd(gc + i, hc[i]);
-  }
-  if (!samp_ticket(&r.tickets[LEVEL], P - 1)) return;
-  const unsigned long long target = static_cast<unsigned long long>(static_cast<double>(q.top_p) * samp::FIX);
-  const unsigned long long base_p = LEVEL == 1 ? 0ull : r.mass_before_p;
-  const long long base_k = LEVEL == 1 ? 0ll : r.cnt_before_k;
-  int fp, fk;
-  unsigned long long bef_p;
-  long long bef_k;
-  samp_scan(gm, gc, do_p, target > base_p ? target - base_p : 0ull, do_k, q.top_k - base_k, fp, bef_p, fk, bef_k);
-  if (threadIdx.x == 0) {
-    if (LEVEL == 1) {
-      r.bp = q.use_p ? fp : samp::NB;
-      r.bk = q.use_k ? fk : samp::NB;
-      r.mass_before_p = bef_p;
-      r.cnt_before_k = static_cast<int>(bef_k);
-    } else {
-      r.sp = do_p ? (fp < samp::NB ? fp : samp::NB - 1) : 0;  // sub-bins <= sp kept
-      r.sk = do_k ? fk : 0;                                   // sub-bins < sk kept
-    }
-  }
+  samp_hist_level<LEVEL>(
+      r, &r.tickets[LEVEL], P, q.use_p, q.use_k, q.top_p, q.top_k,
+      [&](float& M, float& logZ) { samp_row_stats(r, P, M, logZ); },
+      [&](auto f) { sr.visit([&](int, float x) { f(scaled_logit(x, q.it)); }); });
 }
 
 template <typename T>
@@ -574,13 +433,8 @@ __global__ void __launch_bounds__(samp::NT) samp_draw_kernel(const T* __restrict
   sr.visit([&](int i, float x) {
     const float y = scaled_logit(x, q.it);
     if (!q.greedy && y + GMAX < bv) return;
-    if (filt && y < M) {  // the row max is always kept
-      int sub;
-      const int bin = samp_bin(M - y, sub);
-      if (bin >= samp::NB) return;
-      if (q.use_p && bp < samp::NB && (bin > bp || (bin == bp && sub > sp))) return;
-      if (q.use_k && bk < samp::NB && (bin > bk || (bin == bk && sub >= sk))) return;
-    }
+    // the row max is always kept
+    if (filt && y < M && !samp_kept(M - y, q.use_p, bp, sp, q.use_k, bk, sk)) return;
     float score = y;
     if (!q.greedy) {
       const uint32_t hsh = hash32(key ^ hash32(static_cast<uint32_t>(i) * 0x9E3779B9U));

@@ -102,6 +102,9 @@ class EngineConfig:
     # speculate sampled requests too (temperature > 0 without top-p / top-k), verified by
     # rejection sampling (ops.spec_verify_sample); off: they run as plain decodes
     spec_sampled: bool = False
+    # with spec_sampled: also requests with top-p / top-k, verified on the truncated
+    # distributions of draft and target; off: those run as plain decodes
+    spec_truncated: bool = False
     # detokenise / build step N's outputs while step N+1 runs on the GPU (first
     # tokens are still emitted at once, so TTFT is unchanged)
     overlap_outputs: bool = True
@@ -256,7 +259,8 @@ class LLMEngine:
         if cfg.draft_model and cfg.num_speculative_tokens > 0:
             from .spec_decode import SpeculativeDecoder
             self.spec = SpeculativeDecoder(self, cfg.draft_model, cfg.num_speculative_tokens,
-                                           cfg.spec_min_acceptance_rate, sampled=cfg.spec_sampled)
+                                           cfg.spec_min_acceptance_rate, sampled=cfg.spec_sampled,
+                                           truncated=cfg.spec_truncated)
         self._inflight = None  # (plan, handle): launched by the previous step() (async scheduling)
         # Speculative decoding keeps the synchronous loop: asynchronous scheduling plans
         # step N+1 before step N's tokens reach the host, which needs every row's next

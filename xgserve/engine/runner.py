@@ -51,7 +51,8 @@ log = logging.getLogger("xgserve.runner")
 class SpecVerifyRows:
     """The sampled verify blocks of a step (ops.spec_verify_sample), host arrays per block:
     first logits row of the step (in sample order), first row of the draft's kept logits,
-    draft tokens (ks[j] each, concatenated), temperature; one seed per position."""
+    draft tokens (ks[j] each, concatenated), temperature; one seed per position; top_ps /
+    top_ks per block (None: no block is truncated)."""
     p_row0: np.ndarray
     q_row0: np.ndarray
     ks: np.ndarray
@@ -59,6 +60,8 @@ class SpecVerifyRows:
     seeds: np.ndarray
     draft: np.ndarray
     q_logits: torch.Tensor
+    top_ps: Optional[np.ndarray] = None
+    top_ks: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -763,7 +766,8 @@ class ModelRunner:
         nb = len(sv.ks)
         d_off = np.concatenate([[0], np.cumsum(sv.ks)[:-1]])
         _, _, acc = ops.spec_verify_sample(logits, sv.q_logits, sv.draft, sv.p_row0, sv.q_row0, d_off, sv.ks, sv.temps,
-                                           sv.seeds, out_row0=sv.p_row0, out_tok=tok, out_lp=lp)
+                                           sv.seeds, out_row0=sv.p_row0, out_tok=tok, out_lp=lp,
+                                           top_ps=sv.top_ps, top_ks=sv.top_ks)
         if not self.is_cuda:
             self._spec_last = (acc.numpy().copy(),)
             return

@@ -27,13 +27,18 @@ stays below `min_acceptance_rate` (0.5, requirements.md:170) after a few
 verifies stops speculating (its draft pages are freed).
 
 Sampled requests (temperature > 0) are speculated only with `sampled=True`
-(spec.sampled) and only without top-p / top-k: the draft DRAWS its tokens (its
+(spec.sampled), those with top-p / top-k only with `truncated=True` on top of it
+(spec.truncated): the draft DRAWS its tokens (its
 sampler, stream 0 of the position's seed), the logits rows it drew from are kept
 (the definition of q), and the verify step runs ops.spec_verify_sample over those
 blocks after its sampler: draft token i is accepted with probability
 min(1, p(d)/q(d)), the first rejected position emits a token of the residual
 norm(max(0, p - q)), a fully accepted block a bonus token of p -- the output
-follows the target's distribution whatever the draft says. A fixed seed
+follows the target's distribution whatever the draft says. With top-p / top-k the
+draft draws with the request's own top_p / top_k and the verification runs on the
+truncated, renormalised distributions of both models (the kept sets of the sampler),
+so the output follows the truncated target distribution, which is what the plain
+engine samples from. A fixed seed
 reproduces on the same configuration but, unlike greedy, does not equal the
 non-speculating engine's output. Otherwise sampled requests run as plain decodes
 in the same batches.
@@ -72,17 +77,21 @@ class _DraftSeq:
 
 
 class SpeculativeDecoder:
-    def __init__(self, engine, draft_model: str, k: int, min_acceptance_rate: float = 0.5, sampled: bool = False):
+    def __init__(self, engine, draft_model: str, k: int, min_acceptance_rate: float = 0.5, sampled: bool = False,
+                 truncated: bool = False):
         from ..models import build_model, get_config
         self.engine = engine
         self.k = int(k)
         self.min_acceptance_rate = min_acceptance_rate
         self.enabled = engine.is_driver
         self.sampled = bool(sampled)
+        self.truncated = bool(truncated) and self.sampled  # top-p / top-k requests too
         self.proposed = 0
         self.accepted = 0
         self.sampled_proposed = 0   # the part of proposed / accepted that sampled blocks contributed
         self.sampled_accepted = 0
+        self.truncated_proposed = 0  # the part of sampled_* that top-p / top-k blocks contributed
+        self.truncated_accepted = 0
         self.q_buf: Optional[torch.Tensor] = None  # [max_num_seqs * k, V] draft logits rows of sampled proposals
         self.verifies = 0
         self.seqs: Dict[int, _DraftSeq] = {}
@@ -100,6 +109,16 @@ class SpeculativeDecoder:
         if dcfg.vocab_size != engine.mcfg.vocab_size:
             raise ValueError(f"draft vocab {dcfg.vocab_size} != target vocab {engine.mcfg.vocab_size}")
         ec = engine.cfg
+        if self.truncated:
+            # a verify step may hold max_num_seqs truncated blocks of k draft tokens in one
+            # ops.spec_verify_sample call: refuse here what that call would refuse mid-step
+            from ..ops import sampling as _sp
+            n = ec.max_num_seqs
+            need = _sp.spec_ws_need(n * (self.k + 1), n * self.k, dcfg.vocab_size, n * (2 * self.k + 1))
+            if need > _sp.SPEC_WS_CAP:
+                raise ValueError(f"spec_truncated: max_num_seqs={n} with {self.k} speculative tokens needs {need} "
+                                 f"bytes of verify workspace, more than the {_sp.SPEC_WS_CAP} one call may take; "
+                                 f"lower max_num_seqs or num_speculative_tokens")
         bs = ec.block_size
         per_seq = (engine.max_model_len + bs - 1) // bs + 1
         nblocks = int(min(engine.num_blocks, ec.max_num_seqs * per_seq))
@@ -158,6 +177,8 @@ class SpeculativeDecoder:
                 "acceptance_rate": self.accepted / self.proposed if self.proposed else 0.0,
                 "sampled_draft_tokens_proposed": self.sampled_proposed,
                 "sampled_draft_tokens_accepted": self.sampled_accepted,
+                "truncated_draft_tokens_proposed": self.truncated_proposed,
+                "truncated_draft_tokens_accepted": self.truncated_accepted,
                 "verify_steps": self.verifies,
                 "mean_tokens_per_verify": (self.accepted + self.verifies) / self.verifies if self.verifies else 0.0,
                 "spec_step_ms": self.ema_spec_ms, "plain_decode_step_ms": self.ema_plain_ms,
@@ -168,22 +189,35 @@ class SpeculativeDecoder:
         return 0 if self.q_buf is None else self.q_buf.numel() * self.q_buf.element_size()
 
     def _eligible_sampled(self, p) -> bool:
-        return self.sampled and p.temperature > 0 and p.top_p >= 1.0 and p.top_k == 0
+        if not (self.sampled and p.temperature > 0):
+            return False
+        if p.top_p >= 1.0 and p.top_k == 0:
+            return True
+        # top_p = 0, NaN or a negative value is served by the samplers (they keep the first
+        # sub-bin) but is outside what the verify kernels take: such a request decodes plainly.
+        # Decided on the float32 the kernels get: a positive double below 2^-150 is 0 there.
+        with np.errstate(over="ignore"):
+            return bool(self.truncated and np.float32(p.top_p) > 0 and p.top_k >= 0)
+
+    def _is_truncated(self, top_p, top_k) -> bool:
+        """What ops.spec_verify_sample treats as truncated: top_k >= V is off, as 0."""
+        return bool(top_p < 1.0 or 0 < top_k < self.engine.mcfg.vocab_size)
 
     def _draft_samp(self, order, sampled: dict, step: int) -> Optional[SamplingRows]:
         """Sampling rows of a draft step, in its sample order: sampled sequences draw at
-        their temperature (no top-p / top-k) from the seed of output token n + step, the
+        their temperature, top_p and top_k from the seed of output token n + step, the
         engine's mix; greedy ones keep temperature 0. None: every row is greedy."""
         from .engine import position_seeds
         if not any(id(ds) in sampled for ds in order):
             return None
         ns = len(order)
         temps, base, n = np.zeros(ns, np.float32), np.zeros(ns, np.uint64), np.zeros(ns, np.uint64)
+        top_ps, top_ks = np.ones(ns, np.float32), np.zeros(ns, np.int32)
         for i, ds in enumerate(order):
             e = sampled.get(id(ds))
             if e is not None:
-                temps[i], base[i], n[i] = e[1], e[2], e[3] + step
-        return SamplingRows(temps, np.ones(ns, np.float32), np.zeros(ns, np.int32), position_seeds(base, n))
+                temps[i], base[i], n[i], top_ps[i], top_ks[i] = e[1], e[2], e[3] + step, e[4], e[5]
+        return SamplingRows(temps, top_ps, top_ks, position_seeds(base, n))
 
     def _keep_q(self, order, sampled: dict, step: int) -> None:
         """Copy the logits rows the draft sampler just read for the sampled sequences
@@ -284,13 +318,13 @@ class SpeculativeDecoder:
                 ready.append((sid, ds, L))
         if not rows:
             return
-        # sampled sequences of this round: id(ds) -> (first q_buf row, temperature, seed, n)
+        # sampled sequences of this round: id(ds) -> (first q_buf row, temperature, seed, n, top_p, top_k)
         sampled = {}
         for sid, ds, _ in ready:
             req = eng.by_seq[sid]
             if req.params.temperature > 0:
                 sampled[id(ds)] = (len(sampled) * self.k, req.params.temperature, req.params.seed & ((1 << 63) - 1),
-                                   len(req.output_ids))
+                                   len(req.output_ids), req.params.top_p, req.params.top_k)
         plan = self._plan(rows)
         order = [r[0] for r in plan["order"] if r[3]]
         toks, _, _ = self.runner.execute(plan, self._draft_samp(order, sampled, 0))
@@ -372,7 +406,8 @@ class SpeculativeDecoder:
             if tops is not None:
                 out_top.extend(tops[k:k + n + 1])
             k += n_r
-            self._account(int(seq_ids[s]), n_r - 1, n, sampled)
+            self._account(int(seq_ids[s]), n_r - 1, n, sampled,
+                          j in sblock and self._is_truncated(samp.top_ps[j], samp.top_ks[j]))
         plan["_top"] = out_top
         return (np.asarray(out_t, np.int32), np.asarray(out_l, np.float32), hidden, np.asarray(counts, np.int32))
 
@@ -384,7 +419,7 @@ class SpeculativeDecoder:
         from .engine import position_seeds
         sidx, seq_ids, qsl, ids = plan["sample_seq_index"], plan["seq_ids"], plan["query_start_loc"], plan["input_ids"]
         row0 = np.concatenate([[0], np.cumsum(nrows)[:-1]])
-        p0, q0, ks, temps, pseeds, draft = [], [], [], [], [], []
+        p0, q0, ks, temps, pseeds, draft, top_ps, top_ks = [], [], [], [], [], [], [], []
         for j, s in enumerate(sidx.tolist()):
             n_r = int(nrows[j])
             if n_r == 1 or not samp.temps[j] > 0:
@@ -393,6 +428,8 @@ class SpeculativeDecoder:
             ds, req = self.seqs.get(sid), self.engine.by_seq.get(sid)
             if ds is None or req is None or ds.q_row0 < 0 or n_r - 1 > self.k:
                 continue
+            if not (samp.top_ps[j] > 0 and samp.top_ks[j] >= 0):
+                continue  # never proposed (_eligible_sampled); the op would refuse the whole call
             r0 = int(row0[j])
             ps = position_seeds(np.full(n_r, req.params.seed & ((1 << 63) - 1), np.uint64),
                                 len(req.output_ids) + np.arange(n_r, dtype=np.uint64))
@@ -402,21 +439,30 @@ class SpeculativeDecoder:
             q0.append(ds.q_row0)
             ks.append(n_r - 1)
             temps.append(samp.temps[j])
+            top_ps.append(min(float(samp.top_ps[j]), 1.0))  # above 1 is off, as 1
+            top_ks.append(samp.top_ks[j])
             pseeds.append(ps)
             draft.append(ids[int(qsl[s]) + 1:int(qsl[s]) + n_r])
         if not ks:
             return None
+        top_ps, top_ks = np.asarray(top_ps, np.float32), np.asarray(top_ks, np.int32)
+        if not any(self._is_truncated(a, b) for a, b in zip(top_ps, top_ks)):  # the call of before
+            top_ps = top_ks = None
         return SpecVerifyRows(np.asarray(p0, np.int64), np.asarray(q0, np.int64), np.asarray(ks, np.int64),
                               np.asarray(temps, np.float32), np.concatenate(pseeds),
-                              np.concatenate(draft).astype(np.int32), self.q_buf)
+                              np.concatenate(draft).astype(np.int32), self.q_buf, top_ps, top_ks)
 
-    def _account(self, sid: int, proposed: int, accepted: int, sampled: bool = False) -> None:
+    def _account(self, sid: int, proposed: int, accepted: int, sampled: bool = False,
+                 truncated: bool = False) -> None:
         self.proposed += proposed
         self.accepted += accepted
         self.verifies += 1
         if sampled:
             self.sampled_proposed += proposed
             self.sampled_accepted += accepted
+        if truncated:
+            self.truncated_proposed += proposed
+            self.truncated_accepted += accepted
         ds = self.seqs.get(sid)
         if ds is None:
             return

@@ -60,6 +60,24 @@ def argmax_logprob(logits: torch.Tensor, out_tok: Optional[torch.Tensor] = None,
     return out_tok, out_lp
 
 
+def _kept_mask(x: torch.Tensor, logp: torch.Tensor, top_p: float, top_k: int) -> torch.Tensor:
+    """The CPU sampler's exact kept set of one row (x = logits / T, logp its log-softmax):
+    top-k keeps x >= the k-th value, top-p the smallest prefix by sorted probability."""
+    V = x.shape[0]
+    keep = torch.ones(V, dtype=torch.bool, device=x.device)
+    if 0 < top_k < V:
+        kth = torch.topk(x, top_k).values[-1]
+        keep &= x >= kth
+    if top_p < 1.0:
+        sp, si = torch.sort(logp.exp(), descending=True)
+        c = torch.cumsum(sp, 0)
+        n = int((c < top_p).sum()) + 1
+        m = torch.zeros(V, dtype=torch.bool, device=x.device)
+        m[si[:n]] = True
+        keep &= m
+    return keep
+
+
 def _sample_ref(logits, temps, top_ps, top_ks, gen: Optional[torch.Generator]):
     lf = logits.float()
     B, V = lf.shape
@@ -73,19 +91,8 @@ def _sample_ref(logits, temps, top_ps, top_ks, gen: Optional[torch.Generator]):
             continue
         x = lf[i] / t
         logp = torch.log_softmax(x, -1)
-        keep = torch.ones(V, dtype=torch.bool, device=lf.device)
-        k = int(top_ks[i]) if top_ks is not None else 0
-        if 0 < k < V:
-            kth = torch.topk(x, k).values[-1]
-            keep &= x >= kth
-        p = float(top_ps[i]) if top_ps is not None else 1.0
-        if p < 1.0:
-            sp, si = torch.sort(logp.exp(), descending=True)
-            c = torch.cumsum(sp, 0)
-            n = int((c < p).sum()) + 1
-            m = torch.zeros(V, dtype=torch.bool, device=lf.device)
-            m[si[:n]] = True
-            keep &= m
+        keep = _kept_mask(x, logp, float(top_ps[i]) if top_ps is not None else 1.0,
+                          int(top_ks[i]) if top_ks is not None else 0)
         probs = torch.where(keep, logp.exp(), torch.zeros_like(logp))
         j = int(torch.multinomial(probs / probs.sum(), 1, generator=gen))
         toks[i] = j
@@ -227,6 +234,24 @@ def _sample_workspace(device, B: int) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 _SPEC_WS = {}
 _M32 = 0xFFFFFFFF
+# Scratch per logical row of a truncated block (spec::TRow: two 1024-bin histogram levels of
+# u64 mass and u32 counts) and the most one call's workspace may take. 256 MiB holds about
+# 10 900 truncated rows (3 600 blocks of k = 1; 1 500 of k = 3) -- many times a step's worth
+# at max_num_seqs = 256 -- and keeps a mistaken huge call from taking the KV cache's memory.
+SPEC_TROW = 24624
+SPEC_WS_CAP = 256 << 20
+
+
+def spec_ws_need(Lp: int, Lq: int, V: int, n_trunc: int) -> int:
+    """Workspace bytes of a call (spec_ws_bytes of the native library, in Python so that
+    the cap also guards the CPU path): chunk partials, and per truncated row SPEC_TROW plus
+    one float per chunk."""
+    P = max(1, min(64, (512 + Lp - 1) // max(1, Lp)))
+    P = max(1, min(P, (V + 2047) // 2048))
+    base = Lp * P * 32 + (Lp + Lq) * P * 8 + Lp * 8
+    if n_trunc <= 0:
+        return base
+    return ((base + 15) & ~15) + Lp * 16 + n_trunc * SPEC_TROW + n_trunc * P * 4
 
 
 def _hash32i(x: int) -> int:
@@ -296,12 +321,25 @@ def _spec_blocks(p_rows, q_rows, n_draft, n_out, V, p_row0, q_row0, d_off, ks, t
 
 
 def _spec_verify_ref(p_logits, q_logits, draft, p_row0, q_row0, d_off, ks, temps, lrow0, out_row0, seeds, out_tok,
-                     out_lp, accepted) -> None:
+                     out_lp, accepted, top_ps=None, top_ks=None) -> None:
     import numpy as np
     P = p_logits.detach().float().cpu().numpy()
     Q = q_logits.detach().float().cpu().numpy()
     V = P.shape[1]
     rows = {}
+    kept = {}
+
+    def trunc(which, r, t, tp, tk, y):
+        """(kept mask, log of the kept mass) of a truncated row: the kept set is exactly what
+        _sample_ref keeps for this row (the CPU draft sampler drew from it)."""
+        key = (which, r, t.tobytes(), tp, tk)
+        v = kept.get(key)
+        if v is None:
+            x = (p_logits if which == 0 else q_logits)[r].detach().float() / float(t)
+            m = _kept_mask(x, torch.log_softmax(x, -1), tp, tk).numpy()
+            top = y[m].max()
+            v = kept[key] = (m, top + np.log(np.exp(y[m] - top).sum()))
+        return v
 
     def row(which, r, t):  # (y float64, logZ) of a logits row under temperature t, computed once
         key = (which, r, t.tobytes())
@@ -317,11 +355,42 @@ def _spec_verify_ref(p_logits, q_logits, draft, p_row0, q_row0, d_off, ks, temps
     with np.errstate(all="ignore"):
         for j in range(ks.shape[0]):
             k, t = int(ks[j]), temps[j]
+            tp = 1.0 if top_ps is None else float(top_ps[j])
+            tk = 0 if top_ks is None else int(top_ks[j])
+            tr = tp < 1.0 or 0 < tk < V
             a = k
             for i in range(k + 1):
                 seed = int(seeds[lrow0[j] + i])
                 yp, zp = row(0, int(p_row0[j]) + i, t)
                 o = int(out_row0[j]) + i
+                if tr:
+                    # p' / q': -inf off the kept sets, normalised on them; the emitted logprob
+                    # stays y_p - logZ_p of the whole row
+                    mp, ztp = trunc(0, int(p_row0[j]) + i, t, tp, tk, yp)
+                    if i < k:
+                        d = int(draft[d_off[j] + i])
+                        yq, zq = row(1, int(q_row0[j]) + i, t)
+                        mq, ztq = trunc(1, int(q_row0[j]) + i, t, tp, tk, yq)
+                        ok = False
+                        if 0 <= d < V and mp[d]:
+                            u = ((_hash32i(_stream_key(seed, 1)) >> 9) + 0.5) / 8388608.0
+                            ok = bool(not mq[d] or math.log(u) + (yq[d] - ztq) <= yp[d] - ztp)
+                        if ok:
+                            ot[o], ol[o] = d, yp[d] - zp
+                            continue
+                        a = i
+                        lp = np.where(mp, yp - ztp, -np.inf)
+                        lq = np.where(mq, yq - ztq, -np.inf)
+                        keep = mp & (lp > lq)
+                        if keep.any():
+                            w = lp + np.log(-np.expm1(np.where(keep & mq, lq - lp, -np.inf)))
+                            tok = int(np.argmax(np.where(keep, w + _gumbel_row(_stream_key(seed, 2), V), -np.inf)))
+                        else:
+                            tok = int(np.argmax(yp))
+                    else:
+                        tok = int(np.argmax(np.where(mp, yp + _gumbel_row(_stream_key(seed, 2), V), -np.inf)))
+                    ot[o], ol[o] = tok, yp[tok] - zp
+                    break
                 if i < k:
                     d = int(draft[d_off[j] + i])
                     yq, zq = row(1, int(q_row0[j]) + i, t)
@@ -348,8 +417,28 @@ def _spec_verify_ref(p_logits, q_logits, draft, p_row0, q_row0, d_off, ks, temps
             ac[j] = a
 
 
+def _spec_truncation(nb: int, V: int, ks, top_ps, top_ks):
+    """Checked float32 / int32 per-block top_p / top_k (None: off), the first scratch row of
+    every truncated block (-1: the block is untruncated) and the number of such rows."""
+    import numpy as np
+    tps = np.ones(nb, np.float32) if top_ps is None else np.asarray(top_ps, np.float32).reshape(-1)
+    tks = np.zeros(nb, np.int64) if top_ks is None else np.asarray(top_ks, np.int64).reshape(-1)
+    if tps.shape[0] != nb or tks.shape[0] != nb:
+        raise ValueError("spec_verify_sample: top_ps / top_ks need one entry per block")
+    if nb and not (np.isfinite(tps).all() and (tps > 0).all() and (tps <= 1).all()):
+        raise ValueError("spec_verify_sample: top_p must lie in (0, 1]")
+    if nb and tks.min() < 0:
+        raise ValueError("spec_verify_sample: top_k must not be negative")
+    tks = np.minimum(tks, V).astype(np.int32)  # >= V is off, as 0
+    tr = (tps < 1) | ((tks > 0) & (tks < V))
+    rows = np.where(tr, 2 * np.asarray(ks, np.int64) + 1, 0)
+    trow0 = np.where(tr, np.cumsum(rows) - rows, -1)
+    return tps, tks, trow0, int(rows.sum())
+
+
 def spec_verify_sample(p_logits: torch.Tensor, q_logits: torch.Tensor, draft, p_row0, q_row0, d_off, ks, temps, seeds,
-                       out_row0=None, out_tok: Optional[torch.Tensor] = None, out_lp: Optional[torch.Tensor] = None):
+                       out_row0=None, out_tok: Optional[torch.Tensor] = None, out_lp: Optional[torch.Tensor] = None,
+                       top_ps=None, top_ks=None):
     """Speculative-sampling verification of nb blocks in one call. Block j: ks[j] >= 1 draft
     tokens draft[d_off[j]:d_off[j] + k], target rows p_logits[p_row0[j]:p_row0[j] + k + 1],
     draft rows q_logits[q_row0[j]:q_row0[j] + k], temperature temps[j] > 0 (host arrays of
@@ -358,7 +447,13 @@ def spec_verify_sample(p_logits: torch.Tensor, q_logits: torch.Tensor, draft, p_
     Writes, for i <= accepted[j], the emitted token and its log-probability under the
     target at row out_row0[j] + i of out_tok / out_lp (default: positions in block order,
     fresh tensors); rows after that are left alone. Returns (out_tok int32, out_lp fp32,
-    accepted int32 [nb]), on the logits' device; nothing is synchronised."""
+    accepted int32 [nb]), on the logits' device; nothing is synchronised.
+    top_ps / top_ks (host arrays of length nb, None: off): block j verifies against the
+    truncated distributions of its rows, the kept sets of sample_tokens for (temps[j],
+    top_ps[j], top_ks[j]); the logprobs stay those of the whole row. A block with top_p >= 1
+    and top_k of 0 or >= V is untruncated and behaves as without the arrays. Every row of a
+    truncated block needs SPEC_TROW scratch; a call whose workspace would exceed
+    SPEC_WS_CAP bytes raises ValueError (split it into several calls)."""
     import numpy as np
     Rp, V = p_logits.shape
     Rq = q_logits.shape[0]
@@ -385,12 +480,18 @@ def spec_verify_sample(p_logits: torch.Tensor, q_logits: torch.Tensor, draft, p_
     seeds = np.asarray(seeds).astype(np.int64).reshape(-1)
     if seeds.shape[0] != Lp:
         raise ValueError("spec_verify_sample: one seed per position (sum of k + 1)")
+    n_trunc = 0  # without the arrays the call does what it did before they existed
+    if top_ps is not None or top_ks is not None:
+        tps, tks, trow0, n_trunc = _spec_truncation(nb, V, ks, top_ps, top_ks)
     if nb == 0:
         return out_tok, out_lp, accepted
+    if n_trunc and spec_ws_need(Lp, Lq, V, n_trunc) > SPEC_WS_CAP:
+        raise ValueError(f"spec_verify_sample: {n_trunc} truncated rows need more than {SPEC_WS_CAP} bytes of "
+                         f"workspace; verify fewer blocks per call")
     if not use_native(p_logits):
         d = np.asarray(draft, np.int64) if host_draft else draft.numpy()
         _spec_verify_ref(p_logits, q_logits, d, p_row0, q_row0, d_off, ks, temps, lrow0, out_row0, seeds, out_tok,
-                         out_lp, accepted)
+                         out_lp, accepted, tps if n_trunc else None, tks if n_trunc else None)
         return out_tok, out_lp, accepted
     assert p_logits.dtype in (torch.bfloat16, torch.float32)
     K = kernels()
@@ -403,7 +504,10 @@ def spec_verify_sample(p_logits: torch.Tensor, q_logits: torch.Tensor, draft, p_
     blk = h[2 * Lp:2 * Lp + BW * nb].reshape(nb, BW)
     blk[:, 0], blk[:, 1], blk[:, 2], blk[:, 3], blk[:, 4], blk[:, 5] = p_row0, q_row0, d_off, ks, lrow0, out_row0
     blk[:, 6] = temps.view(np.int32)
-    blk[:, 7] = 0
+    if n_trunc:
+        blk[:, 7], blk[:, 8], blk[:, 9] = tks, tps.view(np.int32), trow0
+    else:
+        blk[:, 7], blk[:, 8], blk[:, 9] = 0, 0x3F800000, -1  # top_k off, top_p = 1.0f, no scratch rows
     o_map = 2 * Lp + BW * nb
     idx = np.arange(nb, dtype=np.int32)
     h[o_map:o_map + Lp] = np.repeat(idx, ks + 1)
@@ -414,8 +518,8 @@ def spec_verify_sample(p_logits: torch.Tensor, q_logits: torch.Tensor, draft, p_
     if host_draft:
         draft = d_stage[o_map + Lp + Lq:]
     assert draft.dtype == torch.int32 and draft.is_contiguous() and draft.device == dev
-    need = K.spec_ws_bytes(Lp, Lq, V)
-    # scratch of the three launches, any content on entry; never part of a captured graph,
+    need = K.spec_ws_bytes(Lp, Lq, V, n_trunc)
+    # scratch of the launches, any content on entry; never part of a captured graph,
     # so a grown one simply replaces the old (stream-ordered)
     ws = _SPEC_WS.get((dev.type, dev.index))
     if ws is None or ws.numel() < need:

@@ -143,8 +143,10 @@ class SpecSection:
     draft_model: Optional[str] = None
     num_speculative_tokens: int = 0
     min_acceptance_rate: float = 0.5
-    # speculate sampled requests (temperature > 0, no top-p / top-k) by rejection sampling
+    # speculate sampled requests (temperature > 0; top-p / top-k ones need `truncated`) by rejection sampling
     sampled: bool = False
+    # with `sampled`: also requests with top-p / top-k, verified on the truncated distributions
+    truncated: bool = False
 
 
 @dataclass
@@ -237,6 +239,8 @@ class ServerConfig:
             e.append("degradation thresholds must be increasing in (0, 1]")
         if self.spec.num_speculative_tokens < 0:
             e.append("spec.num_speculative_tokens must be >= 0")
+        if self.spec.truncated and not self.spec.sampled:
+            e.append("spec.truncated requires spec.sampled")
         return e
 
 
