@@ -55,6 +55,37 @@ def _result(x: torch.Tensor, M: int, N: int, S: int, mode: int, out: Optional[to
     return out, 0, out.data_ptr()
 
 
+def _operands(name: str, x: torch.Tensor, w: torch.Tensor, mode: int, out: Optional[torch.Tensor],
+              w_dtype: torch.dtype = torch.bfloat16, int4: bool = False):
+    """The operand check shared by the GEMM wrappers, made before any launch: the kernels
+    take bare pointers and assume dense row-major [M, K] bf16 activations, a dense [N, K]
+    weight (int4 codes: [N, K / 2]) of the dtype they read, one device, and a passed `out`
+    that is exactly the mode's bf16 result. Returns (M, K, N); raises ValueError otherwise."""
+    def bad(what):
+        return ValueError(f"{name}: {what}")
+
+    if x.dim() != 2 or w.dim() != 2:
+        raise bad(f"x and w must be 2-d, got {tuple(x.shape)} and {tuple(w.shape)}")
+    if x.dtype != torch.bfloat16 or w.dtype != w_dtype:
+        raise bad(f"x must be bfloat16 and w {w_dtype}, got {x.dtype} and {w.dtype}")
+    if not x.is_contiguous() or not w.is_contiguous():
+        raise bad("x and w must be contiguous")
+    if x.device != w.device:
+        raise bad(f"x is on {x.device} and w on {w.device}")
+    (M, K), N = x.shape, w.shape[0]
+    if (int4 and K % 2) or w.shape[1] != (K // 2 if int4 else K):
+        raise bad(f"w has {w.shape[1]} columns for K={K}" + (" (int4: K / 2)" if int4 else ""))
+    if out is not None:
+        if mode not in (MODE_BF16, MODE_SILU):
+            raise bad(f"mode {mode} has no `out`")
+        shape = (M, N // 2 if mode == MODE_SILU else N)
+        if (out.dtype != torch.bfloat16 or out.device != x.device or not out.is_contiguous()
+                or tuple(out.shape) != shape):
+            raise bad(f"out must be a contiguous bfloat16 {shape} on {x.device}, got {out.dtype} "
+                      f"{tuple(out.shape)} on {out.device}")
+    return M, K, N
+
+
 def pick_split(N: int, K: int, target_wgs: int = 512) -> int:
     """Smallest split-K giving >= target_wgs workgroups of 32 columns (K % (S*256) == 0).
     512 (two per CU) measured best at M <= 16 on MI355X: Llama-3-8B down_proj 25.2 -> 22.9 us,
@@ -89,8 +120,7 @@ def skinny_linear(x: torch.Tensor, w: torch.Tensor, split_k: Optional[int] = Non
                   out: Optional[torch.Tensor] = None):
     """x [M, K] bf16, w [N, K] bf16 -> bf16 [M, N] (MODE_BF16), PendingSum (MODE_PARTIAL),
     or silu(gate)*up [M, N/2] for a block-16 interleaved gate|up weight (MODE_SILU)."""
-    M, K = x.shape
-    N = w.shape[0]
+    M, K, N = _operands("skinny_gemm", x, w, mode, out)
     S = (split_k or choose_split(M, N, K)) if mode == MODE_PARTIAL else 1
     res, part, outp = _result(x, M, N, S, mode, out)
     kernels().skinny_gemm(x.data_ptr(), M, K, w.data_ptr(), N, part, outp, S, mode, stream_ptr())
@@ -227,10 +257,9 @@ def m64_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, split
     interleaved gate|up weight). With `stats`, x is the raw residual stream and its
     RMSNorm is applied as a per-row epilogue scale rsqrt(sum_sq / K + eps) (the norm
     weight folded into w)."""
-    M, K = x.shape
-    N = w.shape[0]
+    M, K, N = _operands("gemm_m64", x, w, mode, out)
     plan = m64_plan(M, N, K, mode)
-    if (plan is None and None not in (nw, split_k, cfg) and 1 <= M <= M64_MAX_M
+    if (plan is None and None not in (nw, split_k, cfg) and 1 <= M <= M64_MAX_M and cfg in M64G_CFGS
             and _m64_valid(N, K, mode, nw, split_k, cfg, M)):
         plan = (nw, split_k, cfg)  # a fully explicit configuration (sweeps, tests) needs no measured plan
     if plan is None:
@@ -241,8 +270,10 @@ def m64_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, split
         nw = nw or plan[0]
         S = split_k or plan[1]
         cfg = plan[2] if cfg is None else cfg
-        if not _m64_valid(N, K, mode, nw, S, cfg, M):
-            cfg = 0
+        # the configuration that runs is the one that was named: never another in its place
+        if cfg not in M64G_CFGS or not _m64_valid(N, K, mode, nw, S, cfg, M):
+            raise ValueError(f"gemm_m64: (nw, split_k, cfg) = ({nw}, {S}, {cfg}) does not take M={M} N={N} K={K} "
+                             f"mode={mode}")
     res, part, outp = _result(x, M, N, S, mode, out)
     tickets = 0
     if mode == MODE_SILU and S > 1:  # split-K SiLU: slabs + tile tickets, reduced in the GEMM tail
@@ -318,10 +349,9 @@ def mw_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_PARTIAL, plan=N
     """gemm_mw for 1 <= M <= 320 (built for the mixed decode + prefill-chunk step):
     PendingSum (MODE_PARTIAL, reduced by the consumer), bf16 [M, N] (MODE_BF16) or
     silu(gate) * up [M, N / 2] of a block-16 interleaved gate|up weight (MODE_SILU)."""
-    M, K = x.shape
-    N = w.shape[0]
+    M, K, N = _operands("gemm_mw", x, w, mode, out)
     p = plan or mw_plan(M, N, K, mode)
-    if p is None or not x.is_contiguous() or not _mw_fits(M, p[1]):
+    if p is None or not _mw_fits(M, p[1]):
         raise ValueError(f"gemm_mw: unsupported M={M} N={N} K={K} mode={mode}")
     S, cfg = p
     res, part, outp = _result(x, M, N, S, mode, out)
@@ -400,10 +430,9 @@ def pf_linear(x: torch.Tensor, w: torch.Tensor, mode: int = MODE_BF16, plan=None
     """gemm_pf: bf16 [M, N] (MODE_BF16), PendingSum (MODE_PARTIAL, reduced by the
     consumer) or silu(gate) * up [M, N / 2] of a block-16 interleaved gate|up weight
     (MODE_SILU)."""
-    M, K = x.shape
-    N = w.shape[0]
+    M, K, N = _operands("gemm_pf", x, w, mode, out)
     p = plan or pf_plan(M, N, K, mode, cu_count(x.device) if x.is_cuda else 256)
-    if p is None or not x.is_contiguous() or not w.is_contiguous():
+    if p is None:
         raise ValueError(f"gemm_pf: unsupported M={M} N={N} K={K} mode={mode}")
     S, cfg = p[0], p[1]
     res, part, outp = _result(x, M, N, S, mode, out)
@@ -793,13 +822,11 @@ def w8_linear(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, mode: int =
     """x [M <= 64, K] bf16 . W^T with W the dequantized weight (fmt WQ_FP8 / WQ_INT8:
     diag(scale) q; WQ_INT4: group scales): PendingSum (MODE_PARTIAL) or bf16
     silu(gate) * up [M, N/2] from block-16 interleaved gate|up rows (MODE_SILU)."""
-    M, K = x.shape
-    N = q.shape[0]
+    M, K, N = _operands("gemm_w8", x, q, mode, out, w_dtype=torch.uint8, int4=fmt == WQ_INT4)
     p = plan or w8_plan(M, N, K, mode, fmt)
-    kq = K // 2 if fmt == WQ_INT4 else K
-    if (p is None or not x.is_contiguous() or q.dtype != torch.uint8 or scale.dtype != torch.float32
+    if (p is None or scale.dtype != torch.float32 or not scale.is_contiguous() or scale.device != x.device
             or mode not in (MODE_PARTIAL, MODE_SILU)
-            or tuple(q.shape) != (N, kq) or scale.numel() != (N * (K // WQ_GROUP) if fmt == WQ_INT4 else N)):
+            or scale.numel() != (N * (K // WQ_GROUP) if fmt == WQ_INT4 else N)):
         raise ValueError(f"gemm_w8: unsupported M={M} N={N} K={K} mode={mode} fmt={fmt}")
     S, cfg = p[0] if mode == MODE_PARTIAL else 1, p[1]
     res, part, outp = _result(x, M, N, S, mode, out)
