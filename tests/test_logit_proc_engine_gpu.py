@@ -215,7 +215,7 @@ def test_plain_engine_has_no_processor_state(llama_small):
     assert all(len(o) == 8 for o in outs)
     r = eng.runner
     assert r.p_state is None and r.p_scratch is None and not r.proc_graphs and not r.proc_mixed_graphs
-    assert not hasattr(r, "g_pi") and not eng._resets
+    assert r.g_pi is None and not eng._resets
     assert (len(r.graphs), len(r.mixed_graphs)) == (n_graphs, n_mixed)
     torch.cuda.synchronize()
     assert torch.cuda.memory_allocated() - before < (8 << 20)  # nothing the size of a state table or a scratch

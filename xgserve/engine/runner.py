@@ -36,6 +36,7 @@ from .. import ops
 from ..models.base import AttnMeta
 from ..ops.attention import DecodeWorkspace
 from ..parallel import comm
+from .staging import StagingRing, pinned as _pinned
 
 # eager (prompt) steps leave their sampled tokens on the device for a looked-ahead successor
 ASYNC_MIXED = True
@@ -95,9 +96,74 @@ class SamplingRows:
         return self.pens is not None
 
 
-def _pinned(n: int, dtype) -> torch.Tensor:
-    t = torch.empty(n, dtype=dtype)
-    return t.pin_memory() if torch.cuda.is_available() else t
+@dataclass(slots=True)
+class TopRecord:
+    """A step's top-N request: the asking rows, K, the step's sampled rows; ids / lps are the
+    host results of a CPU step (None: they arrive in the step's output set, OutputSet.tops)."""
+    ask: np.ndarray
+    K: int
+    S: int
+    ids: Optional[np.ndarray]
+    lps: Optional[np.ndarray]
+
+
+@dataclass(slots=True)
+class SpecRecord:
+    """A step's sampled verify blocks: their count; acc is accepted[j] of a CPU step (None:
+    it arrives in the step's output set, OutputSet.acc)."""
+    nb: int
+    acc: Optional[np.ndarray]
+
+
+@dataclass(slots=True)
+class StepHandle:
+    """What launch() returns and wait() takes."""
+    n: int = 0                              # sampled rows
+    hidden: Optional[torch.Tensor] = None
+    ready: Optional[tuple] = None           # the host result of a CPU or empty step: nothing to wait for
+    out: Optional[int] = None               # the output set the step's D2H copies write into
+    event: Optional[object] = None          # recorded behind those copies
+    in_gout: bool = False                   # tokens | logprobs in the set's gout (one copy), else in toks / lps
+    on_device: bool = False                 # the sampled tokens also stay in g_out_tok (launched_as_graph)
+    follower_event: Optional[object] = None  # a step of a TP follower: no D2H, an event of this step only
+    top: Optional[TopRecord] = None
+    spec: Optional[SpecRecord] = None
+
+
+class OutputSet:
+    """One of the two sets of pinned D2H targets. A step writes into the set it acquired
+    (StepHandle.out) and records one event behind all its copies; wait() waits on that
+    event, and the set comes round again only after that step was waited on."""
+    __slots__ = ("toks", "lps", "gout", "tops", "tins", "acc")
+
+    def __init__(self, nt: int, OB: int):
+        self.toks = _pinned(nt, torch.int32)        # an eager step's sampled tokens
+        self.lps = _pinned(nt, torch.float32)       # ... and their logprobs
+        self.gout = _pinned(2 * OB, torch.int32)    # a graph step's tokens | logprobs (g_out)
+        self.tops = self.tins = None                # top-N results and inputs (_top_init)
+        self.acc = None                             # accepted[j] of the sampled verify blocks (_spec_launch)
+
+
+def stage_decode_inputs(plan: dict, n: int, bs: int, B: int, W: int, src: Optional[np.ndarray], hi: np.ndarray) -> None:
+    """Host staging of a decode-graph step (ModelRunner._execute_graph): the plan's n rows
+    padded to the bucket bs in the sections ids | positions | slots | seq lens | src (B
+    each) of the int32 buffer `hi` (padding: id 0, position 0, slot -1, seq len 0, src -1),
+    then the first bs block-table rows of width W (the plan's bt_width columns of its n
+    rows are written; the sequence lengths bound what the graph reads)."""
+    hi[0:n] = plan["input_ids"]
+    hi[n:bs] = 0
+    hi[B:B + n] = plan["positions"]
+    hi[B + n:B + bs] = 0
+    hi[2 * B:2 * B + n] = plan["slot_mapping"]
+    hi[2 * B + n:2 * B + bs] = -1
+    hi[3 * B:3 * B + n] = plan["seq_lens"]
+    hi[3 * B + n:3 * B + bs] = 0
+    hi[4 * B:4 * B + bs] = -1
+    if src is not None:
+        hi[4 * B:4 * B + n] = src
+    w = int(plan["bt_width"])
+    bt = hi[5 * B:5 * B + bs * W].reshape(bs, W)
+    bt[:n, :w] = plan["block_tables"].reshape(n, w)
 
 
 def stage_mixed_inputs(plan: dict, Nd: int, nb: int, B: int, C: int, W: int, src: Optional[np.ndarray],
@@ -137,6 +203,11 @@ def stage_mixed_inputs(plan: dict, Nd: int, nb: int, B: int, C: int, W: int, src
 
 
 class ModelRunner:
+    DECODE_SPLIT_WGS = 512
+    # the first launches run under the generous peer-wait limit too (first-call RCCL
+    # communicator setup of a subgroup, first-seen library GEMM shapes)
+    WARM_LAUNCHES = 32
+
     def __init__(self, model, *, block_size: int, num_blocks: int, max_num_seqs: int,
                  max_num_batched_tokens: int, max_model_len: int, use_graphs: bool = True,
                  graph_batch_sizes: Optional[List[int]] = None, is_driver: bool = True,
@@ -169,32 +240,20 @@ class ModelRunner:
         # two pinned host staging buffers + device twins: a step may return
         # before its async H2D copy ran, so the next step must not overwrite the
         # same host buffer until that copy's event has completed
-        self.h_stages = [_pinned(cap, torch.int32) for _ in range(2)]
+        self.stage_ring = StagingRing({"ints": (cap, torch.int32)}, self.is_cuda, units=1)
         self.d_stages = [torch.empty(cap, dtype=torch.int32, device=self.device) for _ in range(2)]
-        self.stage_events = [None, None]
-        self.stage_idx = 0
-        # sampled tokens / logprobs D2H: two pinned buffers + an event each, so a step
-        # launched before the previous one was waited on never overwrites its results
-        nt = max(max_num_batched_tokens, max_num_seqs)
-        self.h_toks = [_pinned(nt, torch.int32) for _ in range(2)]
-        self.h_lps = [_pinned(nt, torch.float32) for _ in range(2)]
-        self.out_idx = 0
         # top-N alternatives: nothing of this exists until a step asks (_top_init)
         self.t_out = None             # static device buffer: ids [n, K] | logprobs [n, K] of the asking rows
         self.top_result = None        # per sampled row of the step wait() last returned: [(id, lp)] or None
-        self._top_last = None
-        self._top_pending: Dict[int, tuple] = {}
         # speculative sampling: accepted[j] of the step's sampled verify blocks, riding the
-        # step's D2H set and event like the top-N results (nothing exists until a step asks)
-        self.h_acc = None
+        # step's output set and event like the top-N results (nothing exists until a step asks)
         self.spec_result = None       # int32 per sampled block of the step wait() last returned, or None
-        self._spec_last = None
-        self._spec_pending: Dict[int, tuple] = {}
         self.sampler_logits = None    # what the last step's sampler read, in sample order
         self.keep_sampler_logits = False  # eager steps too (a speculating draft): holds the tensor a step longer
-        self._es_pin = [None, None]   # eager-step sampling rows: pinned stagings + events
-        self._es_ev = [None, None]
-        self._es_idx = 0
+        # eager-step sampling rows (units: rows): temperatures | top-p, top-k, seeds, and the
+        # processor rows [3, n] / [4, n] of a processed step
+        self.es_ring = StagingRing({"f": (2, torch.float32), "k": (1, torch.int32), "s": (1, torch.int64),
+                                    "pi": (3, torch.int32), "pf": (4, torch.float32)}, self.is_cuda)
         # XGS_TEST_SAMPLE_LOG=1 (tests): every eager sample of this rank, to check that TP
         # followers draw exactly the leader's tokens at temperature > 0
         self.sample_log = [] if os.environ.get("XGS_TEST_SAMPLE_LOG") == "1" else None
@@ -223,15 +282,19 @@ class ModelRunner:
                 self.mixed_chunk = 0
         self._graph_pool = None
         self._init_graph_buffers()
+        # sampled tokens / logprobs D2H: two sets of pinned buffers + an event per step, so a
+        # step launched before the previous one was waited on never overwrites its results
+        nt = max(max_num_batched_tokens, max_num_seqs)
+        self.out_sets = [OutputSet(nt, self.g_OB) for _ in range(2)]
+        self.out_idx = 0              # read and flipped by _acquire_out only
         # logit processors: nothing of this exists until a request asks for one (_proc_init)
+        self.g_pi = self.g_pf = None  # per-row parameters of a graph step
         self.p_state = None           # [max_num_seqs, V] prompt flag | generated count per slot (_state_init)
         self.p_bias_ids = self.p_bias_vals = None   # per-slot logit_bias lists, allocated with the table
         self.p_scratch = None         # fp32 processed logits of a graph step
         self.proc_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (bucket, greedy), captured at first need
         self.proc_mixed_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
-        self._rst_pin = [None, None]  # reset staging: pinned buffers + events
-        self._rst_ev = [None, None]
-        self._rst_idx = 0
+        self.rst_ring = StagingRing({"ints": (1, torch.int32)}, self.is_cuda)  # slot resets (units: words)
         # custom all-reduce peer-wait limit while serving (EngineConfig.collective_timeout_s);
         # warmup, graph capture and the first WARM_LAUNCHES steps run under the warmup limit
         self.collective_timeout_s = 2.0
@@ -242,8 +305,6 @@ class ModelRunner:
     # ------------------------------------------------------------------ utils
     def kv_bytes(self) -> int:
         return self.kv.numel() * self.kv.element_size()
-
-    DECODE_SPLIT_WGS = 512
 
     def decode_splits(self, bs: int) -> int:
         wgs = max(1, bs * self.Hkv)
@@ -277,12 +338,8 @@ class ModelRunner:
         self.g_seed = torch.zeros(B + 1, dtype=torch.int64, device=self.device)
         # two sets of pinned host inputs (event-guarded): the next step's inputs can be
         # written while this step's H2D copies are still queued behind the GPU
-        self.h_ints = [_pinned(n, torch.int32) for _ in range(2)]
-        self.h_samp_fs = [_pinned(2 * (B + 1), torch.float32) for _ in range(2)]
-        self.h_samp_is = [_pinned(B + 1, torch.int32) for _ in range(2)]
-        self.h_samp_ss = [_pinned(B + 1, torch.int64) for _ in range(2)]
-        self.g_stage_events = [None, None]
-        self.g_stage_idx = 0
+        ring = {"ints": (n, torch.int32), "samp_f": (2 * (B + 1), torch.float32), "samp_i": (B + 1, torch.int32),
+                "samp_s": (B + 1, torch.int64)}
         # sampled tokens [0, OB) and their logprobs [OB, 2 OB) in one buffer: a graph step's
         # outputs leave in ONE D2H copy (g_out[:OB + n]) instead of two; OB = B + 1 (a
         # mixed step samples its decode rows + the chunk's last row)
@@ -290,7 +347,6 @@ class ModelRunner:
         self.g_out = torch.zeros(2 * OB, dtype=torch.int32, device=self.device)
         self.g_out_tok = self.g_out[:OB]
         self.g_out_lp = self.g_out[OB:].view(torch.float32)
-        self.h_gout = [_pinned(2 * OB, torch.int32) for _ in range(2)]
         self.g_greedy_graph: Dict[int, bool] = {}
         # mixed-step inputs: ids | pos | slot (B + C rows each) | sl (B + 1) | src (B) |
         # qsl (2) | bt ((B + 1) x W) ; lidx (int64, B + 1)
@@ -305,8 +361,8 @@ class ModelRunner:
             self.m_sl, self.m_src, self.m_qsl = self.m_int[o[3]:o[4]], self.m_int[o[4]:o[5]], self.m_int[o[5]:o[6]]
             self.m_bt = self.m_int[o[6]:].view(B + 1, W)
             self.m_lidx = torch.zeros(B + 1, dtype=torch.int64, device=self.device)
-            self.h_mints = [_pinned(n_m, torch.int32) for _ in range(2)]
-            self.h_mlidx = [_pinned(B + 1, torch.int64) for _ in range(2)]
+            ring.update(mints=(n_m, torch.int32), mlidx=(B + 1, torch.int64))
+        self.g_ring = StagingRing(ring, self.is_cuda, units=1)
 
     def _decode_body(self, bs: int, greedy: bool, proc: bool = False):
         ops.subst_tokens(self.g_ids[:bs], self.g_src[:bs], self.g_out_tok)
@@ -314,18 +370,22 @@ class ModelRunner:
                         dec_block_tables=self.g_bt[:bs], dec_seq_lens=self.g_sl[:bs],
                         num_splits=self.decode_splits(bs), workspace=self.workspace)
         h = self.model(self.g_ids[:bs], meta, self.kv_caches)
-        logits = self.model.compute_logits(h)
+        return self._sample_rows(self.model.compute_logits(h), bs, greedy, proc)
+
+    def _sample_rows(self, logits: torch.Tensor, rows: int, greedy: bool, proc: bool):
+        """The tail of a graph body: process -> argmax or sample into g_out -> state update."""
         if proc:
-            logits = self._process_graph_rows(logits, bs)
+            logits = ops.process_logits(logits, self.p_scratch[:rows], self.p_state, self.g_pi, self.g_pf,
+                                        self.g_temp, self.p_bias_ids, self.p_bias_vals)
         if greedy:
-            ops.argmax_logprob(logits, self.g_out_tok[:bs], self.g_out_lp[:bs])
+            ops.argmax_logprob(logits, self.g_out_tok[:rows], self.g_out_lp[:rows])
         else:
-            tok, lp = ops.sample_tokens(logits, self.g_temp[:bs], self.g_topp[:bs], self.g_topk[:bs],
-                                        self.g_seed[:bs], step=0)
-            self.g_out_tok[:bs].copy_(tok)
-            self.g_out_lp[:bs].copy_(lp)
+            tok, lp = ops.sample_tokens(logits, self.g_temp[:rows], self.g_topp[:rows], self.g_topk[:rows],
+                                        self.g_seed[:rows], step=0)
+            self.g_out_tok[:rows].copy_(tok)
+            self.g_out_lp[:rows].copy_(lp)
         if proc and self.p_state is not None:
-            ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, bs)
+            ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, rows)
         return logits  # what the sampler read: kept by the graph for an eager top_logprobs after a replay
 
     def _mixed_body(self, nb: int, greedy: bool, proc: bool = False):
@@ -350,25 +410,14 @@ class ModelRunner:
                         pre_max_q=C)
         h = self.model(ids_t, meta, self.kv_caches)
         logits = self.model.compute_logits(h.index_select(0, self.m_lidx[:nb + 1]))
-        if proc:
-            logits = self._process_graph_rows(logits, nb + 1)
-        if greedy:
-            ops.argmax_logprob(logits, self.g_out_tok[:nb + 1], self.g_out_lp[:nb + 1])
-        else:
-            tok, lp = ops.sample_tokens(logits, self.g_temp[:nb + 1], self.g_topp[:nb + 1], self.g_topk[:nb + 1],
-                                        self.g_seed[:nb + 1], step=0)
-            self.g_out_tok[:nb + 1].copy_(tok)
-            self.g_out_lp[:nb + 1].copy_(lp)
-        if proc and self.p_state is not None:
-            ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, nb + 1)
-        return logits
+        return self._sample_rows(logits, nb + 1, greedy, proc)
 
     # ------------------------------------------------------------------ logit processors
     def _proc_init(self) -> None:
         """Per-row parameter buffers and the fp32 scratch of graph steps: allocated by the
         first step that is not plain, out of the gpu_memory_utilization headroom (the KV
         pool was sized before)."""
-        if hasattr(self, "g_pi"):
+        if self.g_pi is not None:
             return
         V = self.cfg.vocab_size
         R = self.g_OB
@@ -376,8 +425,7 @@ class ModelRunner:
         self.g_pi = torch.zeros(3, R, dtype=torch.int32, device=self.device)
         self.g_pi[0].fill_(-1)
         self.g_pf = torch.zeros(4, R, dtype=torch.float32, device=self.device)
-        self.h_pis = [_pinned(3 * R, torch.int32) for _ in range(2)]
-        self.h_pfs = [_pinned(4 * R, torch.float32) for _ in range(2)]
+        self.g_ring.add({"pi": (3 * R, torch.int32), "pf": (4 * R, torch.float32)})
         if self.use_graphs:
             self.p_scratch = ops.process_scratch(R, V, self.device)
 
@@ -395,19 +443,13 @@ class ModelRunner:
 
     def _apply_resets(self, resets: list) -> None:
         """Rows of the state table (and bias lists) of newly bound slots, staged through
-        two event-guarded pinned buffers; enqueued on the step's stream, so every update
+        the reset ring; enqueued on the step's stream, so every update
         of the slot's previous owner lands before and the owner's first step after."""
         self._state_init()
         nb = ops.LOGIT_BIAS_MAX
         packed, nres, total = ops.pack_state_resets([r[:3] for r in resets])
         n = packed.size + 2 * nres * nb
-        i = self._rst_idx
-        self._rst_idx ^= 1
-        if self._rst_ev[i] is not None:
-            self._rst_ev[i].synchronize()
-        if self._rst_pin[i] is None or self._rst_pin[i].numel() < n:
-            self._rst_pin[i] = _pinned(max(n, 1 << 16), torch.int32)
-        h = self._rst_pin[i]
+        h = self.rst_ring.acquire(max(n, 1 << 16))["ints"]
         hn = h.numpy()
         hn[:packed.size] = packed
         bi = hn[packed.size:packed.size + nres * nb].reshape(nres, nb)
@@ -418,13 +460,8 @@ class ModelRunner:
             k = len(r[3])
             bi[j, :k] = r[3]
             bv[j, :k] = r[4]
-        if self.is_cuda:
-            d = h[:n].to(self.device, non_blocking=True)
-            ev = self._rst_ev[i] or torch.cuda.Event()
-            ev.record()
-            self._rst_ev[i] = ev
-        else:
-            d = h[:n].clone()
+        d = h[:n].to(self.device, non_blocking=True)
+        self.rst_ring.fence()
         ops.logit_state_reset(self.p_state, d, nres, total)
         for j, r in enumerate(resets):
             if len(r[3]):
@@ -445,18 +482,13 @@ class ModelRunner:
         pf[1:3, n:rows] = 0.0
         pf[3, n:rows] = -np.inf
 
-    def _stage_proc(self, si: int, samp: SamplingRows, n: int, rows: int) -> None:
+    def _stage_proc(self, slot: dict, samp: SamplingRows, n: int, rows: int) -> None:
         """Per-row processor parameters of a graph step -> g_pi / g_pf (rows >= n: plain)."""
         R = self.g_OB
-        hi, hf = self.h_pis[si], self.h_pfs[si]
+        hi, hf = slot["pi"], slot["pf"]
         self._fill_proc_rows(hi.numpy().reshape(3, R), hf.numpy().reshape(4, R), samp, n, rows)
         self.g_pi.view(-1).copy_(hi, non_blocking=True)
         self.g_pf.view(-1).copy_(hf, non_blocking=True)
-
-    def _process_graph_rows(self, logits: torch.Tensor, rows: int) -> torch.Tensor:
-        out = self.p_scratch[:rows]
-        return ops.process_logits(logits, out, self.p_state, self.g_pi, self.g_pf, self.g_temp, self.p_bias_ids,
-                                  self.p_bias_vals)
 
     def _proc_graph(self, key: tuple, mixed: bool):
         """The processed form of a decode (mixed) graph, captured when a step first needs
@@ -541,10 +573,6 @@ class ModelRunner:
         torch.cuda.synchronize()
         return out
 
-    # the first launches run under the generous peer-wait limit too (first-call RCCL
-    # communicator setup of a subgroup, first-seen library GEMM shapes)
-    WARM_LAUNCHES = 32
-
     def _set_comm_timeout(self, seconds: float) -> None:
         from ..parallel.custom_ar import CustomAllReduce
         ar = comm.custom_allreduce()
@@ -602,28 +630,18 @@ class ModelRunner:
         return self.wait(self.launch(plan, samp))
 
     @torch.no_grad()
-    def launch(self, plan: dict, samp: Optional[SamplingRows], src: Optional[np.ndarray] = None):
+    def launch(self, plan: dict, samp: Optional[SamplingRows], src: Optional[np.ndarray] = None) -> StepHandle:
         """Enqueue one step (inputs H2D, forward, sampling, tokens D2H) without
         waiting for it; `wait(handle)` returns what `execute` returns. The host
         can do other work (previous step's detokenisation, planning the next step)
         while the GPU runs. `src` (asynchronous scheduling): per decode row, the
         row of the previous GRAPH step whose sampled token is this row's input
         (-1: the plan's own id)."""
-        self._top_last = None
-        self._spec_last = None
-        h = self._launch(plan, samp, src)
-        if self._top_last is not None:
-            self._top_pending[id(h)] = (h, self._top_last)  # the handle is held: its id stays its own
-        if self._spec_last is not None:
-            self._spec_pending[id(h)] = (h, self._spec_last)
-        return h
-
-    def _launch(self, plan: dict, samp: Optional[SamplingRows], src: Optional[np.ndarray]):
         T = int(plan["num_tokens"])
         Nd = int(plan["num_decodes"])
         ns = int(plan["num_seqs"])
         if T == 0:
-            return (0, None, (None, None, None), None)
+            return StepHandle(ready=(None, None, None))
         if samp is not None and samp.processed:
             self._proc_init()
             if samp.resets:
@@ -642,11 +660,11 @@ class ModelRunner:
                 return self._execute_mixed(plan, samp, Nd, mb, src)
         return self._execute_eager(plan, samp, need_hidden, src)
 
-    def launched_as_graph(self, handle) -> bool:
+    def launched_as_graph(self, handle: StepHandle) -> bool:
         """True if the step left its sampled tokens in g_out_tok (every graph step,
-        and eager steps that qualify for tokens_to_device): the next step may be
+        and eager steps that qualify, _async_ok): the next step may be
         planned and launched before this one completes."""
-        return len(handle) > 4 and handle[4]
+        return handle.on_device
 
     @staticmethod
     def _poll_comm():
@@ -662,16 +680,31 @@ class ModelRunner:
         if ar is not None:
             ar.check()
 
-    def _record_out(self, n: int, tok: torch.Tensor, lp: torch.Tensor, hidden, graph: bool):
-        """Tokens / logprobs D2H into the next of the two pinned buffers + an event."""
-        self._poll_comm()
+    def _acquire_out(self) -> int:
+        """The output set this step's D2H copies go to; the one place that flips out_idx."""
         i = self.out_idx
         self.out_idx ^= 1
-        self.h_toks[i][:n].copy_(tok[:n], non_blocking=True)
-        self.h_lps[i][:n].copy_(lp[:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return (n, hidden, None, (i, ev), graph)
+        return i
+
+    def _record_out(self, h: StepHandle, tok: torch.Tensor, lp: torch.Tensor) -> StepHandle:
+        """Tokens / logprobs D2H into the step's output set + an event."""
+        self._poll_comm()
+        o, n = self.out_sets[h.out], h.n
+        o.toks[:n].copy_(tok[:n], non_blocking=True)
+        o.lps[:n].copy_(lp[:n], non_blocking=True)
+        h.event = torch.cuda.Event()
+        h.event.record()
+        return h
+
+    def _follower_out(self, h: StepHandle) -> StepHandle:
+        """A step of a TP follower: no D2H to wait on, so an event of THIS step -- a
+        follower that queued its successor waits for this launch only
+        (engine.follower_loop), not the whole stream; wait() still drains before the
+        pinned inputs get rewritten."""
+        self._poll_comm()
+        h.follower_event = torch.cuda.Event()
+        h.follower_event.record()
+        return h
 
     @staticmethod
     def _wait_event(ev):
@@ -687,6 +720,27 @@ class ModelRunner:
                 ev.synchronize()
                 return
 
+    def wait(self, handle: StepHandle):
+        res = self._wait(handle)
+        self.top_result = self._top_collect(handle) if handle.top is not None else None
+        self.spec_result = self._spec_collect(handle) if handle.spec is not None else None
+        return res
+
+    def _wait(self, h: StepHandle):
+        if h.ready is not None:
+            return h.ready
+        if h.follower_event is not None:
+            self._wait_event(h.follower_event)  # this step only (TP follower with a successor queued)
+            self._check_comm()
+            return None, None, h.hidden
+        self._wait_event(h.event)  # this step only: a step queued behind it keeps running
+        self._check_comm()
+        o, n = self.out_sets[h.out], h.n
+        if h.in_gout:  # graph step: tokens and logprobs in one pinned buffer
+            OB = self.g_OB
+            return o.gout[:n].numpy().copy(), o.gout[OB:OB + n].view(torch.float32).numpy().copy(), h.hidden
+        return o.toks[:n].numpy().copy(), o.lps[:n].numpy().copy(), h.hidden
+
     # ------------------------------------------------------------------ top-N alternatives
     def _top_init(self) -> None:
         if self.t_out is not None:
@@ -694,15 +748,16 @@ class ModelRunner:
         nt, K = max(self.max_tokens, self.max_num_seqs, self.g_OB), ops.TOPLP_MAX
         self._t_rows = nt
         self.t_out = torch.zeros(2 * nt * K, dtype=torch.int32, device=self.device)
-        # per output buffer (out_idx): results, and the inputs [asking rows | temperatures]
-        self.h_tops = [_pinned(2 * nt * K, torch.int32) for _ in range(2)]
-        self.h_tins = [_pinned(2 * nt, torch.int32) for _ in range(2)]
+        # per output set: results, and the inputs [asking rows | temperatures]
+        for o in self.out_sets:
+            o.tops = _pinned(2 * nt * K, torch.int32)
+            o.tins = _pinned(2 * nt, torch.int32)
 
-    def _top_launch(self, logits: torch.Tensor, samp: SamplingRows) -> None:
+    def _top_launch(self, logits: torch.Tensor, samp: SamplingRows, h: StepHandle) -> None:
         """ops.top_logprobs over the rows of `logits` (what this step's sampler read, in
         sample order) that asked, into the static buffer, and its D2H into the pinned
         buffer of the step's output set -- queued in front of the step's token copy, so the
-        event wait() waits on covers it and the pinned sets are fenced as h_gout is."""
+        event wait() waits on covers it and the pinned sets are fenced as the token buffers are."""
         S = len(samp.temps)
         ask = np.nonzero(samp.topn[:S] > 0)[0].astype(np.int32)
         na = int(ask.shape[0])
@@ -713,12 +768,12 @@ class ModelRunner:
             rows = torch.from_numpy(ask)
             ids, lps = ops.top_logprobs(logits[:S], torch.from_numpy(np.ascontiguousarray(samp.temps, np.float32)), K,
                                         rows)
-            self._top_last = (ask, K, S, ids.numpy(), lps.numpy())
+            h.top = TopRecord(ask, K, S, ids.numpy(), lps.numpy())
             return
         self._top_init()
         assert S <= self._t_rows and logits.shape[0] >= S
-        i = self.out_idx
-        hin = self.h_tins[i]
+        out = self.out_sets[h.out]
+        hin = out.tins
         a = hin.numpy()
         a[:na] = ask
         a[na:na + S].view(np.float32)[:] = samp.temps
@@ -726,31 +781,20 @@ class ModelRunner:
         o = self.t_out
         ops.top_logprobs(logits[:S], d[na:].view(torch.float32), K, d[:na], o[:na * K],
                          o[na * K:2 * na * K].view(torch.float32))
-        self.h_tops[i][:2 * na * K].copy_(o[:2 * na * K], non_blocking=True)
-        self._top_last = (ask, K, S, i)
+        out.tops[:2 * na * K].copy_(o[:2 * na * K], non_blocking=True)
+        h.top = TopRecord(ask, K, S, None, None)
 
-    def _top_collect(self, handle):
-        p = self._top_pending.pop(id(handle), None)
-        if p is None:
-            return None
-        ask, K, S = p[1][:3]
-        na = ask.shape[0]
-        if len(p[1]) == 4:
-            h = self.h_tops[p[1][3]].numpy()
-            ids = h[:na * K].reshape(na, K).copy()
-            lps = h[na * K:2 * na * K].view(np.float32).reshape(na, K).copy()
-        else:
-            ids, lps = p[1][3], p[1][4]
-        top = [None] * S
-        for j, r in enumerate(ask.tolist()):
+    def _top_collect(self, h: StepHandle):
+        t = h.top
+        na, K, ids, lps = t.ask.shape[0], t.K, t.ids, t.lps
+        if ids is None:
+            host = self.out_sets[h.out].tops.numpy()
+            ids = host[:na * K].reshape(na, K).copy()
+            lps = host[na * K:2 * na * K].view(np.float32).reshape(na, K).copy()
+        top = [None] * t.S
+        for j, r in enumerate(t.ask.tolist()):
             top[r] = list(zip(ids[j].tolist(), lps[j].tolist()))
         return top
-
-    def wait(self, handle):
-        res = self._wait(handle)
-        self.top_result = self._top_collect(handle) if self._top_pending else None
-        self.spec_result = self._spec_collect(handle) if self._spec_pending else None
-        return res
 
     # ------------------------------------------------------------------ speculative sampling
     def last_sampler_logits(self) -> Optional[torch.Tensor]:
@@ -759,7 +803,8 @@ class ModelRunner:
         theirs only under keep_sampler_logits)."""
         return self.sampler_logits
 
-    def _spec_launch(self, logits: torch.Tensor, tok: torch.Tensor, lp: torch.Tensor, sv: SpecVerifyRows) -> None:
+    def _spec_launch(self, logits: torch.Tensor, tok: torch.Tensor, lp: torch.Tensor, sv: SpecVerifyRows,
+                     h: StepHandle) -> None:
         """ops.spec_verify_sample over the step's sampled verify blocks: overwrites their
         rows of tok / lp in place; accepted[j] leaves with the step's output set (queued in
         front of the token copy, covered by the event wait() waits on)."""
@@ -769,94 +814,79 @@ class ModelRunner:
                                            sv.seeds, out_row0=sv.p_row0, out_tok=tok, out_lp=lp,
                                            top_ps=sv.top_ps, top_ks=sv.top_ks)
         if not self.is_cuda:
-            self._spec_last = (acc.numpy().copy(),)
+            h.spec = SpecRecord(nb, acc.numpy().copy())
             return
-        if self.h_acc is None:
-            self.h_acc = [_pinned(max(self.max_num_seqs, self.max_tokens), torch.int32) for _ in range(2)]
-        i = self.out_idx
-        self.h_acc[i][:nb].copy_(acc, non_blocking=True)
-        self._spec_last = (i, nb)
+        out = self.out_sets[h.out]
+        if out.acc is None:
+            for o in self.out_sets:
+                o.acc = _pinned(max(self.max_num_seqs, self.max_tokens), torch.int32)
+        out.acc[:nb].copy_(acc, non_blocking=True)
+        h.spec = SpecRecord(nb, None)
 
-    def _spec_collect(self, handle):
-        p = self._spec_pending.pop(id(handle), None)
-        if p is None:
-            return None
-        if len(p[1]) == 1:
-            return p[1][0]
-        i, nb = p[1]
-        return self.h_acc[i][:nb].numpy().copy()
+    def _spec_collect(self, h: StepHandle):
+        if h.spec.acc is not None:
+            return h.spec.acc
+        return self.out_sets[h.out].acc[:h.spec.nb].numpy().copy()
 
-    def _wait(self, handle):
-        n, hidden, ready, out = handle[:4]
-        if ready is not None:
-            return ready
-        if out is None:
-            ev = handle[5] if len(handle) > 5 else None
-            if ev is not None:
-                self._wait_event(ev)  # this step only (TP follower with a successor queued)
-            else:
-                torch.cuda.current_stream().synchronize()
-            self._check_comm()
-            return None, None, hidden
-        i, ev = out[0], out[1]
-        self._wait_event(ev)  # this step only: a step queued behind it keeps running
-        self._check_comm()
-        if len(out) > 2:  # graph step: tokens and logprobs in one pinned buffer
-            OB = out[2]
-            h = self.h_gout[i]
-            return h[:n].numpy().copy(), h[OB:OB + n].view(torch.float32).numpy().copy(), hidden
-        return self.h_toks[i][:n].numpy().copy(), self.h_lps[i][:n].numpy().copy(), hidden
-
+    # ------------------------------------------------------------------ graph steps
     def _execute_graph(self, plan, samp: Optional[SamplingRows], n: int, bs: int, src: Optional[np.ndarray]):
         B, W = self.g_B, self.g_W
         greedy = samp is None or samp.all_greedy
         proc = samp is not None and samp.processed
         graph = self._proc_graph((bs, greedy), False) if proc else self.graphs[(bs, greedy)]
-        si = self.g_stage_idx
-        self.g_stage_idx ^= 1
-        if self.g_stage_events[si] is not None:
-            self.g_stage_events[si].synchronize()  # the H2D copies that last read this set have run
-        h_int = self.h_ints[si]
-        hi = h_int.numpy()
-        w = int(plan["bt_width"])
-        hi[0:n] = plan["input_ids"]
-        hi[n:bs] = 0
-        hi[B:B + n] = plan["positions"]
-        hi[B + n:B + bs] = 0
-        hi[2 * B:2 * B + n] = plan["slot_mapping"]
-        hi[2 * B + n:2 * B + bs] = -1
-        hi[3 * B:3 * B + n] = plan["seq_lens"]
-        hi[3 * B + n:3 * B + bs] = 0
-        hi[4 * B:4 * B + bs] = -1
-        if src is not None:
-            hi[4 * B:4 * B + n] = src
-        bt = hi[5 * B:5 * B + bs * W].reshape(bs, W)
-        bt[:n, :w] = plan["block_tables"].reshape(n, w)
+        slot = self.g_ring.acquire()
+        h_int = slot["ints"]
+        stage_decode_inputs(plan, n, bs, B, W, src, h_int.numpy())
         # ids..src (5*B) and the first bs rows of bt: one contiguous H2D copy
         self.g_int[:5 * B + bs * W].copy_(h_int[:5 * B + bs * W], non_blocking=True)
-        if not greedy or proc:
-            self._stage_sampling(si, samp, n)
+        return self._replay(graph, slot, samp, n, bs, False)
+
+    def _execute_mixed(self, plan, samp: Optional[SamplingRows], Nd: int, nb: int, src: Optional[np.ndarray]):
+        """Replay the (nb, chunk) mixed graph: Nd decode rows at [0, Nd), the prompt
+        chunk's q rows at [B, B + q) of the static input buffers."""
+        B, W, C = self.g_B, self.g_W, self.mixed_chunk
+        greedy = samp is None or samp.all_greedy
+        proc = samp is not None and samp.processed
+        graph = self._proc_graph((nb, greedy), True) if proc else self.mixed_graphs[(nb, greedy)]
+        slot = self.g_ring.acquire()
+        stage_mixed_inputs(plan, Nd, nb, B, C, W, src, self.m_sec, slot["mints"].numpy(), slot["mlidx"].numpy())
+        self.m_int.copy_(slot["mints"], non_blocking=True)
+        self.m_lidx[:nb + 1].copy_(slot["mlidx"][:nb + 1], non_blocking=True)
+        return self._replay(graph, slot, samp, int(plan["num_sample"]), nb + 1, True)
+
+    def _replay(self, graph, slot: dict, samp: Optional[SamplingRows], n: int, rows: int, mixed: bool) -> StepHandle:
+        """The tail of a graph step, its inputs already copied from the ring slot: stage the
+        sampling and processor rows (`rows`: the graph's sampled rows, n of them real),
+        fence the slot, replay, then the step's outputs."""
+        proc = samp is not None and samp.processed
+        if proc or not (samp is None or samp.all_greedy):
+            self._stage_sampling(slot, samp, n)
         if proc:
-            self._stage_proc(si, samp, n, bs)
-        ev = self.g_stage_events[si] or torch.cuda.Event()
-        ev.record()
-        self.g_stage_events[si] = ev
+            self._stage_proc(slot, samp, n, rows)
+        self.g_ring.fence()
         graph.replay()
         self.sampler_logits = graph.xgs_logits
+        h = StepHandle(n=n, on_device=True)
+        if self.is_driver:
+            h.out = self._acquire_out()
         if samp is not None and samp.topn is not None:
-            self._top_launch(graph.xgs_logits, samp)
+            self._top_launch(graph.xgs_logits, samp, h)
+        self.mixed_replays += mixed
         self._log_samples(n)
         if not self.is_driver:
-            # no D2H to wait on; wait() still drains before the pinned inputs get rewritten
-            self._poll_comm()
-            ev = torch.cuda.Event()
-            ev.record()
-            return (n, None, None, None, True, ev)
-        return self._graph_out(n)
+            return self._follower_out(h)
+        # a graph step's n sampled tokens + logprobs (g_out) leave in one D2H copy
+        OB = self.g_OB
+        self._poll_comm()
+        self.out_sets[h.out].gout[:OB + n].copy_(self.g_out[:OB + n], non_blocking=True)
+        h.in_gout = True
+        h.event = torch.cuda.Event()
+        h.event.record()
+        return h
 
-    def _stage_sampling(self, si: int, samp: SamplingRows, n: int) -> None:
+    def _stage_sampling(self, slot: dict, samp: SamplingRows, n: int) -> None:
         """Per-row sampling parameters of a graph step -> g_temp / g_topp / g_topk / g_seed."""
-        hf, hsi, hss = self.h_samp_fs[si], self.h_samp_is[si], self.h_samp_ss[si]
+        hf, hsi, hss = slot["samp_f"], slot["samp_i"], slot["samp_s"]
         OB = self.g_OB
         f = hf.numpy()
         f[:n] = samp.temps
@@ -868,75 +898,22 @@ class ModelRunner:
         self.g_topk[:n].copy_(hsi[:n], non_blocking=True)
         self.g_seed[:n].copy_(hss[:n], non_blocking=True)
 
-    def _graph_out(self, n: int):
-        """Queue a graph step's D2H of its n sampled tokens + logprobs (g_out)."""
-        OB = self.g_OB
-        self._poll_comm()
-        i = self.out_idx
-        self.out_idx ^= 1
-        self.h_gout[i][:OB + n].copy_(self.g_out[:OB + n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return (n, None, None, (i, ev, OB), True)
-
-    def _execute_mixed(self, plan, samp: Optional[SamplingRows], Nd: int, nb: int, src: Optional[np.ndarray]):
-        """Replay the (nb, chunk) mixed graph: Nd decode rows at [0, Nd), the prompt
-        chunk's q rows at [B, B + q) of the static input buffers."""
-        B, W, C = self.g_B, self.g_W, self.mixed_chunk
-        n = int(plan["num_sample"])
-        greedy = samp is None or samp.all_greedy
-        proc = samp is not None and samp.processed
-        graph = self._proc_graph((nb, greedy), True) if proc else self.mixed_graphs[(nb, greedy)]
-        si = self.g_stage_idx
-        self.g_stage_idx ^= 1
-        if self.g_stage_events[si] is not None:
-            self.g_stage_events[si].synchronize()
-        stage_mixed_inputs(plan, Nd, nb, B, C, W, src, self.m_sec, self.h_mints[si].numpy(),
-                           self.h_mlidx[si].numpy())
-        self.m_int.copy_(self.h_mints[si], non_blocking=True)
-        self.m_lidx[:nb + 1].copy_(self.h_mlidx[si][:nb + 1], non_blocking=True)
-        if not greedy or proc:
-            self._stage_sampling(si, samp, n)
-        if proc:
-            self._stage_proc(si, samp, n, nb + 1)
-        ev = self.g_stage_events[si] or torch.cuda.Event()
-        ev.record()
-        self.g_stage_events[si] = ev
-        graph.replay()
-        self.sampler_logits = graph.xgs_logits
-        if samp is not None and samp.topn is not None:
-            self._top_launch(graph.xgs_logits, samp)
-        self.mixed_replays += 1
-        self._log_samples(n)
-        if not self.is_driver:
-            self._poll_comm()
-            ev = torch.cuda.Event()
-            ev.record()
-            return (n, None, None, None, True, ev)
-        return self._graph_out(n)
-
+    # ------------------------------------------------------------------ eager steps
     def _stage_parts(self, parts):
         """The int32 arrays of an eager step -> ONE pinned host buffer -> ONE async H2D
-        copy (two buffers, event-guarded). Returns (device buffer, section offsets)."""
+        copy (the eager ring). Returns (device buffer, section offsets)."""
         sizes = [p.size for p in parts]
         total = sum(sizes)
-        si = self.stage_idx
-        self.stage_idx ^= 1
-        ev = self.stage_events[si]
-        if ev is not None:
-            ev.synchronize()  # the H2D copy that last read this host buffer has run
-        h_stage, d_stage = self.h_stages[si], self.d_stages[si]
+        h_stage = self.stage_ring.acquire()["ints"]
         hs = h_stage.numpy()
         off = 0
         for p in parts:
             hs[off:off + p.size] = p.reshape(-1)
             off += p.size
         if self.is_cuda:
-            d_stage[:total].copy_(h_stage[:total], non_blocking=True)
-            if self.stage_events[si] is None:
-                self.stage_events[si] = torch.cuda.Event()
-            self.stage_events[si].record()
-            dev = d_stage
+            dev = self.d_stages[self.stage_ring.slot]
+            dev[:total].copy_(h_stage[:total], non_blocking=True)
+            self.stage_ring.fence()
         else:
             dev = h_stage
         return dev, np.cumsum([0] + sizes)
@@ -972,132 +949,87 @@ class ModelRunner:
         h = self.model(ids, meta, self.kv_caches)
         hid = h if need_hidden else None
         if S == 0:
-            return (0, hid, (np.zeros(0, np.int32), np.zeros(0, np.float32), hid), None)
+            return StepHandle(hidden=hid, ready=(np.zeros(0, np.int32), np.zeros(0, np.float32), hid))
         logits = self.model.compute_logits(h.index_select(0, lidx.long()))
         if self.capture_logits:
             self.last_logits = logits.float().cpu()
-        if not self.is_driver:
-            if self.is_cuda:
-                # asynchronous prompt steps under TP: when the leader leaves this step's
-                # tokens on the device, so does every follower -- the same all-gathered
-                # logits and the leader's broadcast sampling rows give the same tokens, and
-                # the successor's decode rows substitute their ids from this rank's
-                # g_out_tok exactly as after a graph step
-                on_dev = self._async_ok(S, plan)
-                # a processed step is sampled on every rank even when its tokens stay
-                # unused here: the sampling advances this rank's token statistics
-                if on_dev or (samp is not None and samp.processed):
-                    tok, _ = self._sample(logits, samp)
-                if on_dev:
-                    self.g_out_tok[:S].copy_(tok[:S])
-                    self._log_samples(S)
-                # an event of THIS step: a follower that queued its successor waits
-                # for this launch only (engine.follower_loop), not the whole stream
-                self._poll_comm()
-                ev = torch.cuda.Event()
-                ev.record()
-                return (S, hid, None, None, on_dev, ev)
-            return (S, hid, (None, None, hid), None)
-        tok, lp = self._sample(logits, samp)
-        if self.is_cuda:
-            on_dev = self.tokens_to_device(S, tok, plan)
-            return self._record_out(S, tok, lp, hid, on_dev)
-        return (S, hid, (tok.numpy().astype(np.int32), lp.numpy().astype(np.float32), hid), None)
+        hd = StepHandle(n=S, hidden=hid, out=self._acquire_out() if self.is_driver else None)
+        if not self.is_cuda:
+            if self.is_driver:
+                tok, lp = self._sample(logits, samp, hd)
+                hd.ready = (tok.numpy().astype(np.int32), lp.numpy().astype(np.float32), hid)
+            else:
+                hd.ready = (None, None, hid)
+            return hd
+        # also leave the sampled tokens in g_out_tok, in sample order, so the engine can plan
+        # and launch the next step before this one ends (its decode rows substitute their
+        # ids from there). Asynchronous prompt steps under TP: when the leader leaves this
+        # step's tokens on the device, so does every follower -- the same all-gathered
+        # logits and the leader's broadcast sampling rows give the same tokens, and the
+        # successor's decode rows substitute their ids from this rank's g_out_tok exactly
+        # as after a graph step
+        hd.on_device = self._async_ok(S, plan)
+        # a processed step is sampled on every rank even when its tokens stay unused
+        # there: the sampling advances that rank's token statistics
+        if self.is_driver or hd.on_device or (samp is not None and samp.processed):
+            tok, lp = self._sample(logits, samp, hd)
+        if hd.on_device:
+            self.g_out_tok[:S].copy_(tok[:S])
+            self._log_samples(S)
+        return self._record_out(hd, tok, lp) if self.is_driver else self._follower_out(hd)
 
-    def _sample_processed(self, logits: torch.Tensor, samp: SamplingRows):
-        """The processed form of an eager step's sampling: process_logits -> the sampler
-        on the fp32 scratch -> logit_state_update, parameters staged like _sample's."""
-        n, V = logits.shape
-        pi, pf = np.empty((3, n), np.int32), np.empty((4, n), np.float32)
-        self._fill_proc_rows(pi, pf, samp, n, n)
-        if self.is_cuda:
-            i = self._es_idx
-            self._es_idx ^= 1
-            if self._es_ev[i] is not None:
-                self._es_ev[i].synchronize()
-            if self._es_pin[i] is None or self._es_pin[i][1].numel() < n or len(self._es_pin[i]) < 5:
-                m = max(n, 64)
-                self._es_pin[i] = (_pinned(2 * m, torch.float32), _pinned(m, torch.int32), _pinned(m, torch.int64),
-                                   _pinned(3 * m, torch.int32), _pinned(4 * m, torch.float32))
-            hf, hk, hs, hpi, hpf = self._es_pin[i]
-            f = hf.numpy()
-            f[:n] = samp.temps
-            f[n:2 * n] = samp.top_ps
-            hk.numpy()[:n] = samp.top_ks
-            hs.numpy()[:n] = samp.seeds
-            hpi.numpy()[:3 * n] = pi.reshape(-1)
-            hpf.numpy()[:4 * n] = pf.reshape(-1)
-            dev_f = hf[:2 * n].to(self.device, non_blocking=True).view(2, n)
-            topk = hk[:n].to(self.device, non_blocking=True)
-            seeds = hs[:n].to(self.device, non_blocking=True)
+    def _stage_eager_sampling(self, samp: SamplingRows, n: int, with_proc: bool):
+        """An eager step's sampling rows (with_proc: and its processor rows) through the
+        eager-sampling ring: async H2D -- a follower samples every asynchronous eager
+        step, so no pageable copy or host sync on its step path. Returns the device views
+        temperatures, top-p, top-k, seeds, pi [3, n], pf [4, n] (pi / pf: None without
+        with_proc)."""
+        slot = self.es_ring.acquire(max(n, 64))
+        hf, hk, hs = slot["f"], slot["k"], slot["s"]
+        f = hf.numpy()
+        f[:n] = samp.temps
+        f[n:2 * n] = samp.top_ps
+        hk.numpy()[:n] = samp.top_ks
+        hs.numpy()[:n] = samp.seeds
+        if with_proc:
+            hpi, hpf = slot["pi"], slot["pf"]
+            self._fill_proc_rows(hpi.numpy()[:3 * n].reshape(3, n), hpf.numpy()[:4 * n].reshape(4, n), samp, n, n)
+        dev_f = hf[:2 * n].to(self.device, non_blocking=True).view(2, n)
+        topk = hk[:n].to(self.device, non_blocking=True)
+        seeds = hs[:n].to(self.device, non_blocking=True)
+        d_pi = d_pf = None
+        if with_proc:
             d_pi = hpi[:3 * n].to(self.device, non_blocking=True).view(3, n)
             d_pf = hpf[:4 * n].to(self.device, non_blocking=True).view(4, n)
-            ev = self._es_ev[i] or torch.cuda.Event()
-            ev.record()
-            self._es_ev[i] = ev
-            gen = None
-        else:
-            dev_f = torch.from_numpy(np.stack([samp.temps, samp.top_ps]).astype(np.float32))
-            topk = torch.from_numpy(samp.top_ks.astype(np.int32))
-            seeds = torch.from_numpy(samp.seeds.astype(np.int64))
-            d_pi, d_pf = torch.from_numpy(pi), torch.from_numpy(pf)
-            gen = torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
-        out = ops.process_logits(logits, ops.process_scratch(n, V, logits.device), self.p_state, d_pi, d_pf,
-                                 dev_f[0], self.p_bias_ids, self.p_bias_vals)
-        if samp.all_greedy:
-            tok, lp = ops.argmax_logprob(out)
-        else:
-            tok, lp = ops.sample_tokens(out, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
-        if self.p_state is not None:
-            ops.logit_state_update(self.p_state, d_pi[0], tok, n)
-        if self.keep_sampler_logits:
-            self.sampler_logits = out
-        if samp.topn is not None:
-            self._top_launch(out, samp)
-        return tok, lp
+        self.es_ring.fence()
+        return dev_f[0], dev_f[1], topk, seeds, d_pi, d_pf
 
-    def _sample(self, logits: torch.Tensor, samp: Optional[SamplingRows]):
-        if samp is not None and samp.processed:
-            return self._sample_processed(logits, samp)
-        if samp is None or samp.all_greedy:
+    def _sample(self, logits: torch.Tensor, samp: Optional[SamplingRows], h: StepHandle):
+        """An eager step's sampling: (process_logits into an fp32 scratch ->) argmax or the
+        sampler (-> logit_state_update), then the step's verify blocks and top-N rows."""
+        greedy = samp is None or samp.all_greedy
+        proc = samp is not None and samp.processed
+        if greedy and not proc:
             tok, lp = ops.argmax_logprob(logits)
-        elif self.is_cuda:
-            # eager-step sampling rows through two event-guarded pinned stagings (async
-            # H2D; a follower samples every asynchronous eager step, so no pageable copy
-            # or host sync on its step path)
-            n = len(samp.temps)
-            i = self._es_idx
-            self._es_idx ^= 1
-            if self._es_ev[i] is not None:
-                self._es_ev[i].synchronize()
-            if self._es_pin[i] is None or self._es_pin[i][1].numel() < n:
-                m = max(n, 64)
-                self._es_pin[i] = (_pinned(2 * m, torch.float32), _pinned(m, torch.int32), _pinned(m, torch.int64))
-            hf, hk, hs = self._es_pin[i][:3]
-            f = hf.numpy()
-            f[:n] = samp.temps
-            f[n:2 * n] = samp.top_ps
-            hk.numpy()[:n] = samp.top_ks
-            hs.numpy()[:n] = samp.seeds
-            dev_f = hf[:2 * n].to(self.device, non_blocking=True).view(2, n)
-            topk = hk[:n].to(self.device, non_blocking=True)
-            seeds = hs[:n].to(self.device, non_blocking=True)
-            ev = self._es_ev[i] or torch.cuda.Event()
-            ev.record()
-            self._es_ev[i] = ev
-            tok, lp = ops.sample_tokens(logits, dev_f[0], dev_f[1], topk, seeds, step=0)
         else:
-            dev_f = torch.from_numpy(np.stack([samp.temps, samp.top_ps]).astype(np.float32))
-            topk = torch.from_numpy(samp.top_ks.astype(np.int32))
-            seeds = torch.from_numpy(samp.seeds.astype(np.int64))
-            gen = torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
-            tok, lp = ops.sample_tokens(logits, dev_f[0], dev_f[1], topk, seeds, step=0, generator=gen)
+            n, V = logits.shape
+            temps, top_ps, topk, seeds, d_pi, d_pf = self._stage_eager_sampling(samp, n, proc)
+            if proc:
+                logits = ops.process_logits(logits, ops.process_scratch(n, V, logits.device), self.p_state, d_pi, d_pf,
+                                            temps, self.p_bias_ids, self.p_bias_vals)
+            if greedy:
+                tok, lp = ops.argmax_logprob(logits)
+            else:
+                gen = None if self.is_cuda else torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
+                tok, lp = ops.sample_tokens(logits, temps, top_ps, topk, seeds, step=0, generator=gen)
+            if proc and self.p_state is not None:
+                ops.logit_state_update(self.p_state, d_pi[0], tok, n)
         if self.keep_sampler_logits:
             self.sampler_logits = logits
         if samp is not None and samp.spec is not None:
-            self._spec_launch(logits, tok, lp, samp.spec)
+            self._spec_launch(logits, tok, lp, samp.spec, h)
         if samp is not None and samp.topn is not None:
-            self._top_launch(logits, samp)
+            self._top_launch(logits, samp, h)
         return tok, lp
 
     def _log_samples(self, n: int) -> None:
@@ -1111,15 +1043,3 @@ class ModelRunner:
         The same answer on every TP rank (it depends on the plan only)."""
         return not (not ASYNC_MIXED or not self.graphs or S > self.g_B or bool(plan["is_embed"].any())
                     or int(plan["num_sample"]) != S)
-
-    def tokens_to_device(self, S: int, tok: torch.Tensor, plan: dict) -> bool:
-        """Eager step: also leave the sampled tokens in g_out_tok, in sample order, so
-        the engine can plan and launch the next step before this one ends (its decode
-        rows substitute their ids from there; TP followers do the same from their own
-        sampling, _execute_eager). Verify / embedding steps and batches wider than the
-        graph buffers stay synchronous."""
-        if not self._async_ok(S, plan):
-            return False
-        self.g_out_tok[:S].copy_(tok[:S])
-        self._log_samples(S)
-        return True
