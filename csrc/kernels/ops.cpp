@@ -67,7 +67,12 @@ void segment_sum(const uint16_t*, int, const int32_t*, const int32_t*, float*, i
 void subst_tokens(int32_t*, const int32_t*, const int32_t*, int, hipStream_t);
 int process_logits(const void*, int, int64_t, float*, int64_t, int, int, const uint16_t*, int, const int32_t*,
                    const float*, int, const float*, const int32_t*, const float*, int, float*, hipStream_t);
+int process_logits_hist(const void*, int, int64_t, float*, int64_t, int, int, const uint16_t*, int, const int32_t*,
+                        const float*, int, const float*, const int32_t*, const float*, int, float*, const int32_t*, int,
+                        const int32_t*, hipStream_t);
 int logit_state_reset(uint16_t*, int, int, const int32_t*, int, const int32_t*, const int32_t*, int, hipStream_t);
+int logit_state_add(uint16_t*, int, int, const int32_t*, const int32_t*, int, hipStream_t);
+int logit_hist_max();
 int logit_state_update(uint16_t*, int, int, const int32_t*, const int32_t*, int, hipStream_t);
 int logit_proc_parts(int);
 int logit_bias_max();
@@ -379,6 +384,27 @@ PYBIND11_MODULE(_kernels, m) {
                                   n, S(st)),
           "logit_state_update");
   });
+  // process_logits with per-row extra history: ph = [offset | length] x pstride int32 into the
+  // hist_cap int32 token ids at hist_ids (length <= logit_hist_max())
+  m.def("process_logits_hist", [](uintptr_t in, int is_f32, int64_t in_stride, uintptr_t out, int64_t out_stride,
+                                  int rows, int V, uintptr_t state, int num_slots, uintptr_t pi, uintptr_t pf,
+                                  int pstride, uintptr_t temps, uintptr_t bias_ids, uintptr_t bias_vals, int bias_cap,
+                                  uintptr_t ws, uintptr_t hist_ids, int hist_cap, uintptr_t ph, uintptr_t st) {
+    check(xgk::process_logits_hist(P<const void>(in), is_f32, in_stride, P<float>(out), out_stride, rows, V,
+                                   P<const uint16_t>(state), num_slots, P<const int32_t>(pi), P<const float>(pf),
+                                   pstride, P<const float>(temps), P<const int32_t>(bias_ids),
+                                   P<const float>(bias_vals), bias_cap, P<float>(ws), P<const int32_t>(hist_ids),
+                                   hist_cap, P<const int32_t>(ph), S(st)),
+          "process_logits_hist");
+  });
+  // count[slots[i]][toks[i]] += 1 for i < n; slots and (slot, token) pairs may repeat
+  m.def("logit_state_add", [](uintptr_t state, int num_slots, int V, uintptr_t slots, uintptr_t toks, int n,
+                              uintptr_t st) {
+    check(xgk::logit_state_add(P<uint16_t>(state), num_slots, V, P<const int32_t>(slots), P<const int32_t>(toks), n,
+                               S(st)),
+          "logit_state_add");
+  });
+  m.def("logit_hist_max", &xgk::logit_hist_max);
   m.def("logit_proc_parts", &xgk::logit_proc_parts);
   m.def("logit_bias_max", &xgk::logit_bias_max);
   m.def("logit_count_max", &xgk::logit_count_max);

@@ -105,6 +105,10 @@ class EngineConfig:
     # with spec_sampled: also requests with top-p / top-k, verified on the truncated
     # distributions of draft and target; off: those run as plain decodes
     spec_truncated: bool = False
+    # speculate requests with logit processors (min_p, penalties, logit_bias): every verify
+    # row and every draft row is processed with its own history; off: a speculating engine
+    # refuses them. TP = 1 and at most LOGIT_HIST_MAX speculative tokens
+    spec_processors: bool = False
     # detokenise / build step N's outputs while step N+1 runs on the GPU (first
     # tokens are still emitted at once, so TTFT is unchanged)
     overlap_outputs: bool = True
@@ -256,11 +260,22 @@ class LLMEngine:
                                "prefill_tokens_computed": 0, "requests_finished": 0, "preemptions": 0,
                                "lookahead_launches": 0}
         self.spec = None
+        self.last_plan_seqs: set = set()    # a speculating engine: the sequences of the last plan
+        self.seq_slot: Dict[int, int] = {}  # seq id -> the slot last bound to it (valid while slot_owner agrees)
+        if cfg.spec_processors:
+            from ..ops import LOGIT_HIST_MAX
+            if not (cfg.draft_model and cfg.num_speculative_tokens > 0):
+                raise ValueError("spec_processors requires a draft model and num_speculative_tokens > 0")
+            if cfg.num_speculative_tokens > LOGIT_HIST_MAX:
+                raise ValueError(f"spec_processors allows at most {LOGIT_HIST_MAX} speculative tokens "
+                                 f"(LOGIT_HIST_MAX), got {cfg.num_speculative_tokens}")
+            if st.tp_size > 1:
+                raise ValueError("spec_processors requires TP = 1: the followers' token tables are not kept in step")
         if cfg.draft_model and cfg.num_speculative_tokens > 0:
             from .spec_decode import SpeculativeDecoder
             self.spec = SpeculativeDecoder(self, cfg.draft_model, cfg.num_speculative_tokens,
                                            cfg.spec_min_acceptance_rate, sampled=cfg.spec_sampled,
-                                           truncated=cfg.spec_truncated)
+                                           truncated=cfg.spec_truncated, processors=cfg.spec_processors)
         self._inflight = None  # (plan, handle): launched by the previous step() (async scheduling)
         # Speculative decoding keeps the synchronous loop: asynchronous scheduling plans
         # step N+1 before step N's tokens reach the host, which needs every row's next
@@ -344,9 +359,9 @@ class LLMEngine:
         """What the device path relies on (the HTTP validator checks the documented
         ranges; this guards direct callers too)."""
         from ..ops import LOGIT_BIAS_MAX
-        if self.spec is not None:
+        if self.spec is not None and not self.cfg.spec_processors:
             # verification samples k + 1 positions of a row in one step, each with a
-            # different history: processed verification is not built
+            # different history: that form of the processors needs spec_processors
             names = [n for n, neutral in (("min_p", 0.0), ("repetition_penalty", 1.0), ("presence_penalty", 0.0),
                                           ("frequency_penalty", 0.0), ("logit_bias", {}))
                      if getattr(params, n) != neutral]
@@ -387,6 +402,7 @@ class LLMEngine:
         req.finish_time = time.monotonic()
         self.requests.pop(req.request_id, None)
         self.by_seq.pop(req.seq_id, None)
+        self.seq_slot.pop(req.seq_id, None)
         self.stats_counters["requests_finished"] += 1
 
     def has_work(self) -> bool:
@@ -401,7 +417,11 @@ class LLMEngine:
         for i in stale.tolist():
             s, sid = int(slots[i]), int(sids[i])
             r = self.by_seq.get(sid)
+            prev = self.seq_slot.get(sid)
+            if prev is not None and prev != s and self.slot_owner[prev] == sid:
+                self.slot_owner[prev] = -1  # its row there is stale from now on: bound afresh if it returns
             self.slot_owner[s] = sid
+            self.seq_slot[sid] = s
             self.slot_req[s] = r
             self.slot_ngen[s] = len(r.output_ids) if r is not None else 0
             self.slot_pen[:, s] = (1.0, 0.0, 0.0, -np.inf)
@@ -615,6 +635,8 @@ class LLMEngine:
                 outs += self._flush_deferred()  # the draft needs every request's tokens
                 self.spec.propose()
             plan = self.sched.schedule()
+            if self.spec is not None:
+                self.last_plan_seqs = set(plan["seq_ids"].tolist())
         t = self._tick("schedule", t)
         st = get_state()
         samp = None

@@ -80,6 +80,14 @@ class SamplingRows:
     # slots bound since the last processed step, reset ahead of this one on every rank:
     # [(slot, unique ids, cells, bias ids, bias values)]
     resets: Optional[list] = None
+    # per-row extra history (speculation: a verify block's rows, a draft step's rows): an
+    # int32 token list and int32 [2, rows] = offset | length (<= LOGIT_HIST_MAX) into it;
+    # None: the step enqueues the processors without it
+    hist_ids: Optional[np.ndarray] = None
+    hist_pos: Optional[np.ndarray] = None
+    # the slots of the in-step logit_state_update where they differ from `slots` (-1 for
+    # the rows of a verify block, whose emitted tokens are committed after acceptance)
+    upd_slots: Optional[np.ndarray] = None
     # top-N alternatives (ops.top_logprobs): int32 entries asked per row, None: no row asked
     # and the step enqueues nothing for them
     topn: Optional[np.ndarray] = None
@@ -253,7 +261,9 @@ class ModelRunner:
         # eager-step sampling rows (units: rows): temperatures | top-p, top-k, seeds, and the
         # processor rows [3, n] / [4, n] of a processed step
         self.es_ring = StagingRing({"f": (2, torch.float32), "k": (1, torch.int32), "s": (1, torch.int64),
-                                    "pi": (3, torch.int32), "pf": (4, torch.float32)}, self.is_cuda)
+                                    "pi": (3, torch.int32), "pf": (4, torch.float32),
+                                    # extra history: offset | length | update slot, and the token list
+                                    "ph": (3, torch.int32), "hl": (ops.LOGIT_HIST_MAX, torch.int32)}, self.is_cuda)
         # XGS_TEST_SAMPLE_LOG=1 (tests): every eager sample of this rank, to check that TP
         # followers draw exactly the leader's tokens at temperature > 0
         self.sample_log = [] if os.environ.get("XGS_TEST_SAMPLE_LOG") == "1" else None
@@ -295,6 +305,12 @@ class ModelRunner:
         self.proc_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (bucket, greedy), captured at first need
         self.proc_mixed_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self.rst_ring = StagingRing({"ints": (1, torch.int32)}, self.is_cuda)  # slot resets (units: words)
+        # read-only processor mode (a speculating draft): the table and bias lists are
+        # proc_source's, never updated, reset or allocated here (set_proc_source)
+        self.proc_source: Optional["ModelRunner"] = None
+        self.g_ph = self.g_hist = None  # per-row extra history of a graph step (proc_hist runners)
+        self.proc_hist = False          # processed graph steps take per-row extra history
+        self.add_ring = StagingRing({"ints": (2, torch.int32)}, self.is_cuda)  # commit_tokens (units: entries)
         # custom all-reduce peer-wait limit while serving (EngineConfig.collective_timeout_s);
         # warmup, graph capture and the first WARM_LAUNCHES steps run under the warmup limit
         self.collective_timeout_s = 2.0
@@ -376,7 +392,8 @@ class ModelRunner:
         """The tail of a graph body: process -> argmax or sample into g_out -> state update."""
         if proc:
             logits = ops.process_logits(logits, self.p_scratch[:rows], self.p_state, self.g_pi, self.g_pf,
-                                        self.g_temp, self.p_bias_ids, self.p_bias_vals)
+                                        self.g_temp, self.p_bias_ids, self.p_bias_vals,
+                                        self.g_hist if self.proc_hist else None, self.g_ph if self.proc_hist else None)
         if greedy:
             ops.argmax_logprob(logits, self.g_out_tok[:rows], self.g_out_lp[:rows])
         else:
@@ -384,7 +401,7 @@ class ModelRunner:
                                         self.g_seed[:rows], step=0)
             self.g_out_tok[:rows].copy_(tok)
             self.g_out_lp[:rows].copy_(lp)
-        if proc and self.p_state is not None:
+        if proc and self.p_state is not None and self.proc_source is None:
             ops.logit_state_update(self.p_state, self.g_pi[0], self.g_out_tok, rows)
         return logits  # what the sampler read: kept by the graph for an eager top_logprobs after a replay
 
@@ -426,14 +443,48 @@ class ModelRunner:
         self.g_pi[0].fill_(-1)
         self.g_pf = torch.zeros(4, R, dtype=torch.float32, device=self.device)
         self.g_ring.add({"pi": (3 * R, torch.int32), "pf": (4 * R, torch.float32)})
+        if self.proc_hist:  # [offset | length] per row, row i's list at i * LOGIT_HIST_MAX
+            H = ops.LOGIT_HIST_MAX
+            self.g_ph = torch.zeros(2, R, dtype=torch.int32, device=self.device)
+            self.g_hist = torch.zeros(R * H, dtype=torch.int32, device=self.device)
+            self.g_ring.add({"ph": (2 * R, torch.int32), "hl": (R * H, torch.int32)})
         if self.use_graphs:
             self.p_scratch = ops.process_scratch(R, V, self.device)
+
+    def set_proc_source(self, source: "ModelRunner") -> None:
+        """Read-only processor mode: this runner processes its rows against `source`'s state
+        table and bias lists (same device), with per-row extra history in its graph steps.
+        It never enqueues logit_state_update, never applies resets and never allocates a
+        table; the table is aliased again at every launch, as the source allocates its own
+        at its first request that needs one (the processed graphs are keyed on it)."""
+        assert source.device == self.device and source.cfg.vocab_size == self.cfg.vocab_size
+        self.proc_source = source
+        self.proc_hist = True
+
+    def _alias_proc_source(self) -> None:
+        src = self.proc_source
+        self.p_state, self.p_bias_ids, self.p_bias_vals = src.p_state, src.p_bias_ids, src.p_bias_vals
+
+    def commit_tokens(self, slots: np.ndarray, toks: np.ndarray) -> None:
+        """count[slot][token] += 1 for the emitted tokens of verify blocks (entries may repeat
+        a slot and a pair): ops.logit_state_add on the step's stream, ahead of whatever
+        reads the table next."""
+        n = int(len(slots))
+        if n == 0 or self.p_state is None:
+            return
+        h = self.add_ring.acquire(max(n, 64))["ints"]
+        hn = h.numpy()
+        hn[:n] = slots
+        hn[n:2 * n] = toks
+        d = h[:2 * n].to(self.device, non_blocking=True)
+        self.add_ring.fence()
+        ops.logit_state_add(self.p_state, d[:n], d[n:], n)
 
     def _state_init(self) -> None:
         """The state table and the per-slot bias lists: allocated by the first request
         that needs token statistics (min_p alone does not). Processed graphs captured
         before hold no table; they are keyed apart from those captured after."""
-        if self.p_state is not None:
+        if self.p_state is not None or self.proc_source is not None:
             return
         V, ns, nb = self.cfg.vocab_size, self.max_num_seqs, ops.LOGIT_BIAS_MAX
         self.p_state = ops.logit_state_alloc(ns, V, self.device)
@@ -489,6 +540,21 @@ class ModelRunner:
         self._fill_proc_rows(hi.numpy().reshape(3, R), hf.numpy().reshape(4, R), samp, n, rows)
         self.g_pi.view(-1).copy_(hi, non_blocking=True)
         self.g_pf.view(-1).copy_(hf, non_blocking=True)
+        if self.proc_hist:
+            H = ops.LOGIT_HIST_MAX
+            hp, hl = slot["ph"], slot["hl"]
+            ph = hp.numpy().reshape(2, R)
+            ph[:] = 0
+            if samp.hist_pos is not None:
+                # every row's own copy of its list at row * H: the graph's list has a fixed layout
+                ops.check_hist_pos(samp.hist_pos, len(samp.hist_ids), n)
+                lst = hl.numpy().reshape(R, H)
+                for i in range(n):
+                    o, ln = int(samp.hist_pos[0, i]), int(samp.hist_pos[1, i])
+                    lst[i, :ln] = samp.hist_ids[o:o + ln]
+                    ph[0, i], ph[1, i] = i * H, ln
+                self.g_hist[:n * H].copy_(hl[:n * H], non_blocking=True)
+            self.g_ph.view(-1).copy_(hp, non_blocking=True)
 
     def _proc_graph(self, key: tuple, mixed: bool):
         """The processed form of a decode (mixed) graph, captured when a step first needs
@@ -497,7 +563,7 @@ class ModelRunner:
         no tracked slot) and the static buffers get their contents back afterwards."""
         graphs = self.proc_mixed_graphs if mixed else self.proc_graphs
         n, greedy = key
-        key = (n, greedy, self.p_state is not None)
+        key = (n, greedy, self.p_state is not None)  # (a read-only runner: its source's table, aliased at launch)
         g = graphs.get(key)
         if g is not None:
             return g
@@ -509,6 +575,8 @@ class ModelRunner:
             self._neutral_inputs(mixed)
             self.g_pi[0].fill_(-1)
             self.g_pi[2].zero_()
+            if self.g_ph is not None:
+                self.g_ph.zero_()
             g = self._warm_and_capture([(key, body)], warm=1, error_mode="thread_local")[key]
         for t, c in zip(keep, saved):
             t.copy_(c)
@@ -642,10 +710,11 @@ class ModelRunner:
         ns = int(plan["num_seqs"])
         if T == 0:
             return StepHandle(ready=(None, None, None))
-        if samp is not None and samp.processed:
-            self._proc_init()
-            if samp.resets:
-                self._apply_resets(samp.resets)
+        if self.proc_source is not None:
+            self._alias_proc_source()
+        if samp is not None and samp.processed and samp.resets:
+            assert self.proc_source is None, "a read-only runner applies no resets"
+            self._apply_resets(samp.resets)
         if self._warm_launches:
             self._warm_launches -= 1
             if self._warm_launches == 0:
@@ -833,6 +902,8 @@ class ModelRunner:
         B, W = self.g_B, self.g_W
         greedy = samp is None or samp.all_greedy
         proc = samp is not None and samp.processed
+        if proc:
+            self._proc_init()
         graph = self._proc_graph((bs, greedy), False) if proc else self.graphs[(bs, greedy)]
         slot = self.g_ring.acquire()
         h_int = slot["ints"]
@@ -847,6 +918,8 @@ class ModelRunner:
         B, W, C = self.g_B, self.g_W, self.mixed_chunk
         greedy = samp is None or samp.all_greedy
         proc = samp is not None and samp.processed
+        if proc:
+            self._proc_init()
         graph = self._proc_graph((nb, greedy), True) if proc else self.mixed_graphs[(nb, greedy)]
         slot = self.g_ring.acquire()
         stage_mixed_inputs(plan, Nd, nb, B, C, W, src, self.m_sec, slot["mints"].numpy(), slot["mlidx"].numpy())
@@ -983,7 +1056,8 @@ class ModelRunner:
         eager-sampling ring: async H2D -- a follower samples every asynchronous eager
         step, so no pageable copy or host sync on its step path. Returns the device views
         temperatures, top-p, top-k, seeds, pi [3, n], pf [4, n] (pi / pf: None without
-        with_proc)."""
+        with_proc), ph [3, n] = history offset | length | update slot and the history token
+        list (None unless the rows carry them)."""
         slot = self.es_ring.acquire(max(n, 64))
         hf, hk, hs = slot["f"], slot["k"], slot["s"]
         f = hf.numpy()
@@ -997,12 +1071,27 @@ class ModelRunner:
         dev_f = hf[:2 * n].to(self.device, non_blocking=True).view(2, n)
         topk = hk[:n].to(self.device, non_blocking=True)
         seeds = hs[:n].to(self.device, non_blocking=True)
-        d_pi = d_pf = None
+        d_pi = d_pf = d_ph = d_hl = None
         if with_proc:
             d_pi = hpi[:3 * n].to(self.device, non_blocking=True).view(3, n)
             d_pf = hpf[:4 * n].to(self.device, non_blocking=True).view(4, n)
+            if samp.hist_pos is not None or samp.upd_slots is not None:
+                # offset | length | update slot per row, and the step's token list
+                nl = 0 if samp.hist_ids is None else len(samp.hist_ids)
+                assert nl <= n * ops.LOGIT_HIST_MAX
+                hph, hhl = slot["ph"], slot["hl"]
+                ph = hph.numpy()[:3 * n].reshape(3, n)
+                ph[:2] = 0
+                if samp.hist_pos is not None:
+                    ops.check_hist_pos(samp.hist_pos, nl, n)
+                    ph[:2] = samp.hist_pos[:, :n]
+                    hhl.numpy()[:nl] = samp.hist_ids
+                ph[2] = samp.slots if samp.upd_slots is None else samp.upd_slots
+                d_ph = hph[:3 * n].to(self.device, non_blocking=True).view(3, n)
+                if samp.hist_pos is not None:
+                    d_hl = hhl[:max(nl, 1)].to(self.device, non_blocking=True)[:nl]
         self.es_ring.fence()
-        return dev_f[0], dev_f[1], topk, seeds, d_pi, d_pf
+        return dev_f[0], dev_f[1], topk, seeds, d_pi, d_pf, d_ph, d_hl
 
     def _sample(self, logits: torch.Tensor, samp: Optional[SamplingRows], h: StepHandle):
         """An eager step's sampling: (process_logits into an fp32 scratch ->) argmax or the
@@ -1013,17 +1102,19 @@ class ModelRunner:
             tok, lp = ops.argmax_logprob(logits)
         else:
             n, V = logits.shape
-            temps, top_ps, topk, seeds, d_pi, d_pf = self._stage_eager_sampling(samp, n, proc)
+            temps, top_ps, topk, seeds, d_pi, d_pf, d_ph, d_hl = self._stage_eager_sampling(samp, n, proc)
             if proc:
+                hist = d_hl is not None
                 logits = ops.process_logits(logits, ops.process_scratch(n, V, logits.device), self.p_state, d_pi, d_pf,
-                                            temps, self.p_bias_ids, self.p_bias_vals)
+                                            temps, self.p_bias_ids, self.p_bias_vals, d_hl if hist else None,
+                                            d_ph[:2].view(2, n) if hist else None)
             if greedy:
                 tok, lp = ops.argmax_logprob(logits)
             else:
                 gen = None if self.is_cuda else torch.Generator().manual_seed(int(samp.seeds[0]) & 0x7FFFFFFF)
                 tok, lp = ops.sample_tokens(logits, temps, top_ps, topk, seeds, step=0, generator=gen)
-            if proc and self.p_state is not None:
-                ops.logit_state_update(self.p_state, d_pi[0], tok, n)
+            if proc and self.p_state is not None and self.proc_source is None:
+                ops.logit_state_update(self.p_state, d_pi[0] if d_ph is None else d_ph[2], tok, n)
         if self.keep_sampler_logits:
             self.sampler_logits = logits
         if samp is not None and samp.spec is not None:

@@ -43,6 +43,18 @@ reproduces on the same configuration but, unlike greedy, does not equal the
 non-speculating engine's output. Otherwise sampled requests run as plain decodes
 in the same batches.
 
+Requests with logit processors (min_p, penalties, logit_bias) are speculated only with
+`processors=True` (spec.processors). Row i of a verify block is processed as the
+non-speculating engine would process it had the block's first i draft tokens been
+emitted: its history is the slot's committed row of the state table plus those i tokens
+(ops.process_logits with per-row extra history). The draft processes the rows it draws
+from the same way -- the target's table, read-only, plus the tokens drafted so far this
+round -- so it proposes what the processed target accepts. After the acceptance test the
+block's emitted tokens are added to the table (ops.logit_state_add) before anything
+reads it again. With the key on, the draft's kept rows are fp32 and a verify step with a
+sampled block is run processed (plain rows with neutral parameters): the widening is
+exact, so plain requests draw what they draw with the key off.
+
 TP > 1: the draft lives only on the leader (TP=1 weights); followers execute the
 verify plan broadcast with every other step.
 """
@@ -61,6 +73,10 @@ from .runner import ModelRunner, SamplingRows, SpecVerifyRows
 log = logging.getLogger("xgserve.spec")
 
 MIN_VERIFIES = 3
+# sampled requests with min_p > 0: their processed rows hold -inf where min_p masked a
+# token; speculated only if ops.spec_verify_sample agrees with its reference on such rows
+# (tests/test_spec_proc_gpu.py), else they decode plainly, as top_p = 0 does
+SAMPLED_MIN_P = True
 
 
 @dataclass
@@ -74,11 +90,12 @@ class _DraftSeq:
     verifies: int = 0
     disabled: bool = False
     q_row0: int = -1         # sampled proposal of this round: first row of the kept draft logits
+    slot: int = -1           # processed proposal of this round: the engine slot whose table row it read
 
 
 class SpeculativeDecoder:
     def __init__(self, engine, draft_model: str, k: int, min_acceptance_rate: float = 0.5, sampled: bool = False,
-                 truncated: bool = False):
+                 truncated: bool = False, processors: bool = False):
         from ..models import build_model, get_config
         self.engine = engine
         self.k = int(k)
@@ -92,6 +109,9 @@ class SpeculativeDecoder:
         self.sampled_accepted = 0
         self.truncated_proposed = 0  # the part of sampled_* that top-p / top-k blocks contributed
         self.truncated_accepted = 0
+        self.processors = bool(processors)  # requests with logit processors too
+        self.processed_proposed = 0  # the part of proposed / accepted that processed requests contributed
+        self.processed_accepted = 0
         self.q_buf: Optional[torch.Tensor] = None  # [max_num_seqs * k, V] draft logits rows of sampled proposals
         self.verifies = 0
         self.seqs: Dict[int, _DraftSeq] = {}
@@ -127,6 +147,8 @@ class SpeculativeDecoder:
                                   max_num_batched_tokens=ec.max_num_batched_tokens, max_model_len=engine.max_model_len,
                                   use_graphs=ec.use_graphs, graph_batch_sizes=ec.graph_batch_sizes, is_driver=True)
         self.runner.keep_sampler_logits = self.sampled
+        if self.processors:  # the draft reads the target's table and bias lists, never writes them
+            self.runner.set_proc_source(engine.runner)
         self.runner.capture_graphs()
         self.free: List[int] = list(range(nblocks - 1, -1, -1))
         log.info("speculative decoding: draft=%s k=%d draft KV pages=%d", draft_model, self.k, nblocks)
@@ -179,6 +201,8 @@ class SpeculativeDecoder:
                 "sampled_draft_tokens_accepted": self.sampled_accepted,
                 "truncated_draft_tokens_proposed": self.truncated_proposed,
                 "truncated_draft_tokens_accepted": self.truncated_accepted,
+                "processed_draft_tokens_proposed": self.processed_proposed,
+                "processed_draft_tokens_accepted": self.processed_accepted,
                 "verify_steps": self.verifies,
                 "mean_tokens_per_verify": (self.accepted + self.verifies) / self.verifies if self.verifies else 0.0,
                 "spec_step_ms": self.ema_spec_ms, "plain_decode_step_ms": self.ema_plain_ms,
@@ -203,12 +227,16 @@ class SpeculativeDecoder:
         """What ops.spec_verify_sample treats as truncated: top_k >= V is off, as 0."""
         return bool(top_p < 1.0 or 0 < top_k < self.engine.mcfg.vocab_size)
 
-    def _draft_samp(self, order, sampled: dict, step: int) -> Optional[SamplingRows]:
+    def _draft_samp(self, order, sampled: dict, step: int, proc: Optional[dict] = None,
+                    drafts: Optional[dict] = None) -> Optional[SamplingRows]:
         """Sampling rows of a draft step, in its sample order: sampled sequences draw at
         their temperature, top_p and top_k from the seed of output token n + step, the
-        engine's mix; greedy ones keep temperature 0. None: every row is greedy."""
+        engine's mix; greedy ones keep temperature 0. Processed sequences (proc: id(ds) ->
+        engine slot) get their slot's parameters and, as extra history, the tokens drafted
+        so far this round (drafts: id(ds) -> list). None: every row is greedy and plain."""
         from .engine import position_seeds
-        if not any(id(ds) in sampled for ds in order):
+        has_proc = bool(proc) and any(id(ds) in proc for ds in order)
+        if not has_proc and not any(id(ds) in sampled for ds in order):
             return None
         ns = len(order)
         temps, base, n = np.zeros(ns, np.float32), np.zeros(ns, np.uint64), np.zeros(ns, np.uint64)
@@ -217,7 +245,25 @@ class SpeculativeDecoder:
             e = sampled.get(id(ds))
             if e is not None:
                 temps[i], base[i], n[i], top_ps[i], top_ks[i] = e[1], e[2], e[3] + step, e[4], e[5]
-        return SamplingRows(temps, top_ps, top_ks, position_seeds(base, n))
+        rows = SamplingRows(temps, top_ps, top_ks, position_seeds(base, n))
+        if has_proc:
+            eng = self.engine
+            rows.slots, rows.bias_lens = np.full(ns, -1, np.int32), np.zeros(ns, np.int32)
+            rows.pens = np.zeros((4, ns), np.float32)
+            rows.pens[0], rows.pens[3] = 1.0, -np.inf
+            hist, pos = [], np.zeros((2, ns), np.int32)
+            for i, ds in enumerate(order):
+                s = proc.get(id(ds))
+                if s is None:
+                    continue
+                rows.slots[i], rows.bias_lens[i], rows.pens[:, i] = eng.slot_track[s], eng.slot_blen[s], eng.slot_pen[:, s]
+                d = drafts.get(id(ds)) if drafts else None
+                if d and eng.slot_track[s] >= 0:
+                    pos[0, i], pos[1, i] = len(hist), len(d)
+                    hist.extend(d)
+            if hist:
+                rows.hist_ids, rows.hist_pos = np.asarray(hist, np.int32), pos
+        return rows
 
     def _keep_q(self, order, sampled: dict, step: int) -> None:
         """Copy the logits rows the draft sampler just read for the sampled sequences
@@ -227,13 +273,16 @@ class SpeculativeDecoder:
         if not src:
             return
         logits = self.runner.last_sampler_logits()
+        # with processors the kept rows are fp32, as processed rows are: a step's p and q
+        # rows must be of one dtype (plain bf16 rows are widened here, which is exact)
+        dt = torch.float32 if self.processors else logits.dtype
         if self.q_buf is None:  # lazily, at the first sampled proposal
-            self.q_buf = torch.zeros(self.engine.cfg.max_num_seqs * self.k, logits.shape[1], dtype=logits.dtype,
+            self.q_buf = torch.zeros(self.engine.cfg.max_num_seqs * self.k, logits.shape[1], dtype=dt,
                                      device=logits.device)
         dst = [sampled[id(order[i])][0] + step for i in src]
         dev = logits.device
         self.q_buf.index_copy_(0, torch.tensor(dst, dtype=torch.long, device=dev),
-                               logits.index_select(0, torch.tensor(src, dtype=torch.long, device=dev)))
+                               logits.index_select(0, torch.tensor(src, dtype=torch.long, device=dev)).to(dt))
 
     # ------------------------------------------------------------------ draft steps
     def _plan(self, rows) -> dict:
@@ -275,6 +324,7 @@ class SpeculativeDecoder:
         budget = self.runner.max_tokens
         rows, ready = [], []
         for sid, ds in self.seqs.items():
+            ds.slot = -1
             if ds.q_row0 >= 0:
                 # a sampled proposal the scheduler has not verified: its q rows are about to be
                 # reused, so the draft is withdrawn (re-proposed below if still eligible)
@@ -283,12 +333,27 @@ class SpeculativeDecoder:
         for sid, req in eng.by_seq.items():
             if req.finished or req.kind == RequestType.Embeddings or not req.output_ids:
                 continue
+            if sid not in eng.last_plan_seqs:
+                # not running (pre-empted, waiting to be resumed): a draft set now would ride
+                # its recompute step, which is a prompt row and verifies nothing
+                continue
             p = req.params
             if (p.temperature > 0 and not self._eligible_sampled(p)) or len(req.output_ids) + 1 >= p.max_tokens:
                 continue
+            slot = -1
+            if not p.plain:
+                # a processed proposal reads the slot's row of the target's table: the slot must
+                # be bound to this sequence, and its row current (a pending reset: stale until
+                # the next processed target step)
+                slot = eng.seq_slot.get(sid, -1)
+                if not self.processors or slot < 0 or eng.slot_owner[slot] != sid or slot in eng._resets:
+                    continue
+                if p.temperature > 0 and p.min_p > 0 and not SAMPLED_MIN_P:
+                    continue
             ds = self.seqs.get(sid)
             if ds is None:
                 ds = self.seqs[sid] = _DraftSeq(blocks=[])
+            ds.slot = slot
             if ds.disabled:
                 continue
             if ds.pending_L >= 0:  # last proposal was never verified: trust only the real tokens
@@ -325,9 +390,10 @@ class SpeculativeDecoder:
             if req.params.temperature > 0:
                 sampled[id(ds)] = (len(sampled) * self.k, req.params.temperature, req.params.seed & ((1 << 63) - 1),
                                    len(req.output_ids), req.params.top_p, req.params.top_k)
+        proc = {id(ds): ds.slot for _, ds, _ in ready if ds.slot >= 0}
         plan = self._plan(rows)
         order = [r[0] for r in plan["order"] if r[3]]
-        toks, _, _ = self.runner.execute(plan, self._draft_samp(order, sampled, 0))
+        toks, _, _ = self.runner.execute(plan, self._draft_samp(order, sampled, 0, proc))
         if not ready:
             return
         self._keep_q(order, sampled, 0)
@@ -337,7 +403,8 @@ class SpeculativeDecoder:
             drows = [(ds, [drafts[sid][-1]], L + step - 1, True) for sid, ds, L in ready]
             dplan = self._plan(drows)
             dorder = [r[0] for r in dplan["order"]]
-            t2, _, _ = self.runner.execute(dplan, self._draft_samp(dorder, sampled, step))
+            so_far = {id(ds): drafts[sid] for sid, ds, _ in ready if ds.slot >= 0}
+            t2, _, _ = self.runner.execute(dplan, self._draft_samp(dorder, sampled, step, proc, so_far))
             self._keep_q(dorder, sampled, step)
             by_ds = {id(r[0]): int(t) for r, t in zip(dplan["order"], t2)}
             for sid, ds, _ in ready:
@@ -370,12 +437,17 @@ class SpeculativeDecoder:
                                  np.repeat(samp.top_ks, nrows), seeds, spec=sv)
             if samp.topn is not None:
                 rsamp.topn = np.repeat(samp.topn, nrows)
+            if samp.processed or (self.processors and sv is not None):
+                # (a step with a sampled block is run processed, plain rows neutral: its kept
+                # q rows are fp32, and p and q must be of one dtype)
+                self._processed_rows(plan, samp, rsamp, nrows)
         toks, lps, hidden = self.engine.runner.execute(plan, rsamp)
         if toks is None:
             return None, None, hidden, None
         acc = self.engine.runner.spec_result  # accepted[b] of the sampled blocks, same D2H and event as toks
         out_t, out_l, counts = [], [], []
         tops = self.engine.runner.top_result  # per verify row; sliced to the accepted positions as lps
+        c_slots, c_toks = [], []  # (slot, token) of every token a tracked verify block emitted
         out_top = [] if tops is not None else None
         k = 0
         for j, s in enumerate(sidx.tolist()):
@@ -408,8 +480,42 @@ class SpeculativeDecoder:
             k += n_r
             self._account(int(seq_ids[s]), n_r - 1, n, sampled,
                           j in sblock and self._is_truncated(samp.top_ps[j], samp.top_ks[j]))
+            if samp is not None and samp.slots is not None and samp.slots[j] >= 0:
+                c_slots.extend([int(samp.slots[j])] * (n + 1))
+                c_toks.extend(int(x) for x in t[:n + 1])
+        if c_slots:
+            # the blocks' emitted tokens become history before the next proposal or step
+            self.engine.runner.commit_tokens(np.asarray(c_slots, np.int32), np.asarray(c_toks, np.int32))
         plan["_top"] = out_top
         return (np.asarray(out_t, np.int32), np.asarray(out_l, np.float32), hidden, np.asarray(counts, np.int32))
+
+    def _processed_rows(self, plan: dict, samp: SamplingRows, rsamp: SamplingRows, nrows: np.ndarray) -> None:
+        """Processor parameters of the repeated rows: every row of a block gets its
+        sequence's slot, bias list and penalties; row i of a tracked block the block's first
+        i draft tokens as extra history (one staged list: the blocks' drafts, concatenated).
+        The in-step table update is left to single rows (q_len 1, prompts): a block's
+        emitted tokens are committed after the acceptance test."""
+        ns = len(nrows)
+        if samp.processed:
+            slots, blens, pens = samp.slots, samp.bias_lens, samp.pens
+        else:
+            slots, blens = np.full(ns, -1, np.int32), np.zeros(ns, np.int32)
+            pens = np.zeros((4, ns), np.float32)
+            pens[0], pens[3] = 1.0, -np.inf
+        rsamp.slots, rsamp.bias_lens = np.repeat(slots, nrows), np.repeat(blens, nrows)
+        rsamp.pens = np.repeat(pens, nrows, axis=1)
+        rsamp.resets = samp.resets
+        rsamp.upd_slots = np.repeat(np.where(nrows == 1, slots, -1).astype(np.int32), nrows)
+        sidx, qsl, ids = plan["sample_seq_index"], plan["query_start_loc"], plan["input_ids"]
+        hist, pos, r = [], np.zeros((2, int(nrows.sum())), np.int32), 0
+        for j, s in enumerate(sidx.tolist()):
+            n_r = int(nrows[j])
+            if n_r > 1 and slots[j] >= 0:
+                pos[0, r:r + n_r], pos[1, r:r + n_r] = len(hist), np.arange(n_r)
+                hist.extend(int(x) for x in ids[int(qsl[s]) + 1:int(qsl[s]) + n_r])
+            r += n_r
+        if hist:
+            rsamp.hist_ids, rsamp.hist_pos = np.asarray(hist, np.int32), pos
 
     def _sampled_blocks(self, plan: dict, samp: SamplingRows, nrows: np.ndarray, seeds: np.ndarray,
                         sblock: dict) -> Optional[SpecVerifyRows]:
@@ -463,6 +569,10 @@ class SpeculativeDecoder:
         if truncated:
             self.truncated_proposed += proposed
             self.truncated_accepted += accepted
+        req = self.engine.by_seq.get(sid)
+        if req is not None and not req.params.plain:
+            self.processed_proposed += proposed
+            self.processed_accepted += accepted
         ds = self.seqs.get(sid)
         if ds is None:
             return

@@ -15,7 +15,8 @@ from .sampling import argmax_logprob, sample_tokens, argmax_logprob_ref, segment
 from .sampling import top_logprobs, top_logprobs_ref, TOPLP_MAX
 from .sampling import spec_verify_sample
 from .sampling import (process_logits, process_scratch, logit_state_alloc, logit_state_cells, logit_state_reset,
-                       logit_state_update, pack_state_resets, LOGIT_BIAS_MAX)
+                       logit_state_update, logit_state_add, check_hist_pos, pack_state_resets, LOGIT_BIAS_MAX,
+                       LOGIT_HIST_MAX)
 from .embedding import embed_gather, mean_l2norm_rows
 from .moe import (moe_topk_softmax, moe_route, moe_route_norm, moe_align, moe_forward_ref, fused_moe, ep_plan,
                   ep_scatter, ep_combine)
@@ -30,7 +31,7 @@ __all__ = [
     "argmax_logprob", "sample_tokens", "argmax_logprob_ref", "segment_sum", "subst_tokens",
     "spec_verify_sample",
     "process_logits", "process_scratch", "logit_state_alloc", "logit_state_cells", "logit_state_reset",
-    "logit_state_update", "pack_state_resets", "LOGIT_BIAS_MAX",
+    "logit_state_update", "logit_state_add", "check_hist_pos", "pack_state_resets", "LOGIT_BIAS_MAX", "LOGIT_HIST_MAX",
     "embed_gather", "mean_l2norm_rows",
     "moe_topk_softmax", "moe_route", "moe_route_norm", "moe_align", "moe_forward_ref", "fused_moe", "ep_plan", "ep_scatter", "ep_combine",
     "native_available",

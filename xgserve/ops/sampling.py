@@ -542,6 +542,7 @@ LOGIT_BIAS_MAX = 128       # logit_bias entries per request (LP_BIAS_MAX)
 LOGIT_COUNT_MAX = 0x7FFF   # a cell's generated-count saturates here
 LOGIT_PROMPT_FLAG = 0x8000  # cell bit 15: the token occurs in the prompt
 _LOGIT_CHUNK = 4096        # LP_CHUNK: tokens per workgroup
+LOGIT_HIST_MAX = 16        # extra-history tokens per row of process_logits (LP_HIST_MAX)
 
 
 def logit_state_alloc(num_slots: int, vocab: int, device) -> torch.Tensor:
@@ -618,6 +619,45 @@ def logit_state_update(state: torch.Tensor, slots: torch.Tensor, toks: torch.Ten
     kernels().logit_state_update(state.data_ptr(), S, V, slots.data_ptr(), toks.data_ptr(), n, stream_ptr())
 
 
+def logit_state_add(state: torch.Tensor, slots: torch.Tensor, toks: torch.Tensor, n: int) -> None:
+    """count[slots[i]][toks[i]] += 1 (saturating, prompt flag kept) for every i < n; int32
+    inputs. Unlike logit_state_update, entries may repeat a slot and a (slot, token) pair:
+    the commit of the tokens a verify block emitted. Entries with a slot or a token out of
+    range are skipped. The table needs an even number of cells (the kernel updates the
+    aligned 32-bit word that holds a cell)."""
+    S, V = state.shape
+    assert slots.dtype == toks.dtype == torch.int32 and slots.numel() >= n and toks.numel() >= n
+    assert state.is_contiguous()
+    if n <= 0:
+        return
+    if not use_native(state):
+        st = state.numpy().view("uint16")
+        for s, t in zip(slots[:n].tolist(), toks[:n].tolist()):
+            if 0 <= s < S and 0 <= t < V and (st[s, t] & LOGIT_COUNT_MAX) < LOGIT_COUNT_MAX:
+                st[s, t] += 1
+        return
+    if (S * V) % 2:
+        raise ValueError("logit_state_add: the state table needs an even number of cells")
+    assert slots.is_contiguous() and toks.is_contiguous()
+    kernels().logit_state_add(state.data_ptr(), S, V, slots.data_ptr(), toks.data_ptr(), n, stream_ptr())
+
+
+def check_hist_pos(hist_pos, n_ids: int, rows: Optional[int] = None) -> None:
+    """ValueError on what process_logits' extra history would index out of range: hist_pos
+    (host int32 [2, R] = offset | length) against a list of n_ids tokens."""
+    import numpy as np
+    hp = np.asarray(hist_pos)
+    if hp.ndim != 2 or hp.shape[0] != 2:
+        raise ValueError("process_logits: hist_pos must be [2, R] = offset | length")
+    off, ln = hp[0, :rows].astype(np.int64), hp[1, :rows].astype(np.int64)
+    if off.size == 0:
+        return
+    if ln.min() < 0 or ln.max() > LOGIT_HIST_MAX:
+        raise ValueError(f"process_logits: a row's extra history must have 0..{LOGIT_HIST_MAX} tokens")
+    if off.min() < 0 or (off + ln).max() > n_ids:
+        raise ValueError("process_logits: a row's extra history leaves the token list")
+
+
 _PROC_WS = {}
 
 
@@ -638,13 +678,31 @@ def process_scratch(rows: int, V: int, device) -> torch.Tensor:
 
 def process_logits(logits: torch.Tensor, out: torch.Tensor, state: Optional[torch.Tensor], pi: torch.Tensor,
                    pf: torch.Tensor, temps: torch.Tensor, bias_ids: Optional[torch.Tensor] = None,
-                   bias_vals: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   bias_vals: Optional[torch.Tensor] = None, hist_ids: Optional[torch.Tensor] = None,
+                   hist_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[i] = processed fp32 logits of row i (bf16 or fp32 `logits`, any row stride).
     pi: int32 [3, R] = slot (-1: no history) | offset into bias_ids / bias_vals | number
     of bias entries; pf: fp32 [4, R] = repetition | frequency | presence penalty |
-    ln(min_p) (-inf: off); temps: fp32 [>= rows] (min_p applies where temps > 0); R >= rows."""
+    ln(min_p) (-inf: off); temps: fp32 [>= rows] (min_p applies where temps > 0); R >= rows.
+    hist_ids (int32 token list) and hist_pos (int32 [2, R] = offset | length into it, length
+    <= LOGIT_HIST_MAX): row i is processed as if the listed tokens had been generated after
+    what its slot's table row holds -- a token's count is raised by its multiplicity in the
+    list (saturating, prompt flag kept); ids outside [0, V) are ignored; rows of a verify
+    block share one list and differ in length. Host (CPU) positions are checked here; the
+    positions of a device call are checked by whoever stages them (check_hist_pos) and the
+    kernel drops a list that would leave hist_ids. Without the two the call is the one of
+    before they existed."""
     rows, V = logits.shape
     R = pi.shape[1]
+    hist = hist_pos is not None
+    if hist:
+        if hist_ids is None:
+            raise ValueError("process_logits: hist_pos without hist_ids")
+        assert hist_ids.dtype == torch.int32 and hist_pos.dtype == torch.int32
+        assert tuple(hist_pos.shape) == (2, R) and hist_pos.is_contiguous() and hist_ids.is_contiguous()
+        assert hist_ids.device == logits.device and hist_pos.device == logits.device
+        if hist_pos.device.type == "cpu":
+            check_hist_pos(hist_pos.numpy(), hist_ids.numel(), rows)
     assert pi.dtype == torch.int32 and pf.dtype == torch.float32 and temps.dtype == torch.float32
     assert pi.shape[0] == 3 and tuple(pf.shape) == (4, R) and R >= rows and temps.numel() >= rows
     assert pi.is_contiguous() and pf.is_contiguous() and temps.is_contiguous()
@@ -652,10 +710,18 @@ def process_logits(logits: torch.Tensor, out: torch.Tensor, state: Optional[torc
     assert state is None or (state.shape[1] == V and state.is_contiguous())
     cap = 0 if bias_ids is None else min(bias_ids.numel(), bias_vals.numel())
     if not use_native(logits):
-        _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals)
+        _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals, hist_ids if hist else None,
+                            hist_pos)
         return out
     assert logits.dtype in (torch.bfloat16, torch.float32)
     ws = _proc_ws(logits.device, rows, V)
+    if hist:
+        kernels().process_logits_hist(logits.data_ptr(), 1 if logits.dtype == torch.float32 else 0, logits.stride(0),
+                                      out.data_ptr(), out.stride(0), rows, V, ptr(state),
+                                      0 if state is None else state.shape[0], pi.data_ptr(), pf.data_ptr(), R,
+                                      temps.data_ptr(), ptr(bias_ids), ptr(bias_vals), cap, ws.data_ptr(),
+                                      hist_ids.data_ptr(), hist_ids.numel(), hist_pos.data_ptr(), stream_ptr())
+        return out
     kernels().process_logits(logits.data_ptr(), 1 if logits.dtype == torch.float32 else 0, logits.stride(0),
                              out.data_ptr(), out.stride(0), rows, V, ptr(state),
                              0 if state is None else state.shape[0], pi.data_ptr(), pf.data_ptr(), R,
@@ -663,7 +729,7 @@ def process_logits(logits: torch.Tensor, out: torch.Tensor, state: Optional[torc
     return out
 
 
-def _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals) -> None:
+def _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals, hist_ids=None, hist_pos=None) -> None:
     import numpy as np
     f32 = np.float32
     rows, V = logits.shape
@@ -678,6 +744,13 @@ def _process_logits_ref(logits, out, state, pi, pf, temps, bias_ids, bias_vals) 
             r, f, p, lm = f32(pfn[0, i]), f32(pfn[1, i]), f32(pfn[2, i]), f32(pfn[3, i])
             cell = st[slot] if (st is not None and 0 <= slot < st.shape[0]) else np.zeros(V, np.uint16)
             c = (cell & LOGIT_COUNT_MAX).astype(np.int32)
+            if hist_pos is not None:
+                # the row's extra history: counts raised by the multiplicities, flag kept
+                hoff, hlen = int(hist_pos[0, i]), int(hist_pos[1, i])
+                h = hist_ids.numpy()[hoff:hoff + hlen].astype(np.int64)
+                h = h[(h >= 0) & (h < V)]
+                c = np.minimum(c + np.bincount(h, minlength=V).astype(np.int32), LOGIT_COUNT_MAX)
+                cell = (cell & LOGIT_PROMPT_FLAG) | c.astype(np.uint16)
             x = np.where(cell != 0, np.where(x > 0, x / r, x * r), x).astype(f32)
             x = (x - (f * c.astype(f32)).astype(f32)).astype(f32)
             x = np.where(c > 0, x - p, x).astype(f32)

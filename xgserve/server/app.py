@@ -149,7 +149,8 @@ def _result_lp(r):
 
 def _validate_processors(srv: InferenceServer, req) -> None:
     """Ranges of the sampling extensions (400, `Invalid parameter '<field>': <reason>`);
-    a server that decodes speculatively accepts plain requests only."""
+    a server that decodes speculatively accepts plain requests only, unless it was
+    started with spec.processors."""
     InferenceServer._raise_validation(srv.validator.check_top_logprobs(int(req.top_logprobs)))
     res = srv.validator.check_processors(req.min_p, req.repetition_penalty, req.presence_penalty,
                                          req.frequency_penalty, list(req.logit_bias.keys()),
@@ -158,7 +159,7 @@ def _validate_processors(srv: InferenceServer, req) -> None:
     InferenceServer._raise_validation(res)
     spec = getattr(srv.cfg, "spec", None)
     speculating = spec is not None and spec.draft_model and spec.num_speculative_tokens > 0
-    if speculating:
+    if speculating and not getattr(spec, "processors", False):
         for name, neutral in (("min_p", 0.0), ("repetition_penalty", 1.0), ("presence_penalty", 0.0),
                               ("frequency_penalty", 0.0), ("logit_bias", {})):
             if getattr(req, name) != neutral:

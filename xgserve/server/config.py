@@ -147,6 +147,10 @@ class SpecSection:
     sampled: bool = False
     # with `sampled`: also requests with top-p / top-k, verified on the truncated distributions
     truncated: bool = False
+    # speculate requests with min_p, penalties or logit_bias too (every verify row processed
+    # with its own history); off: such requests are answered with a 400. TP = 1, at most
+    # LOGIT_HIST_MAX (16) speculative tokens; the draft's kept logits rows are fp32
+    processors: bool = False
 
 
 @dataclass
@@ -241,6 +245,14 @@ class ServerConfig:
             e.append("spec.num_speculative_tokens must be >= 0")
         if self.spec.truncated and not self.spec.sampled:
             e.append("spec.truncated requires spec.sampled")
+        if self.spec.processors:
+            if not (self.spec.draft_model and self.spec.num_speculative_tokens > 0):
+                e.append("spec.processors requires spec.draft_model and spec.num_speculative_tokens > 0")
+            if self.spec.num_speculative_tokens > 16:
+                e.append("spec.processors allows at most 16 speculative tokens (LOGIT_HIST_MAX), got "
+                         f"spec.num_speculative_tokens={self.spec.num_speculative_tokens}")
+            if w.tp > 1:
+                e.append("spec.processors requires worker.tp = 1 (the followers' token tables are not kept in step)")
         return e
 
 

@@ -58,6 +58,7 @@ def engine_spec(worker, cache=None, spec=None, fault: Optional[dict] = None, bat
                 min_acceptance_rate=0.5 if spec is None else spec.min_acceptance_rate,
                 spec_sampled=False if spec is None else bool(spec.sampled),
                 spec_truncated=False if spec is None else bool(spec.truncated),
+                spec_processors=False if spec is None else bool(getattr(spec, "processors", False)),
                 prompt_coalesce=1 if batcher is None else batcher.coalesce_prompts,
                 prompt_coalesce_max_wait=4 if batcher is None else batcher.coalesce_max_wait_steps,
                 fault=dict(fault or {}))
