@@ -721,17 +721,17 @@ class Want:
 
 
 # ---------------------------------------------------------------- guarded buffers
-def guarded(shape, dtype, dev):
-    """(whole sentinel-filled buffer, its interior view of `shape`)."""
+def guarded(shape, dtype, dev, pad=PAD):
+    """(whole sentinel-filled buffer, its interior view of `shape`); `pad` sentinels on each side."""
     n = math.prod(shape)
     it, sent = (torch.int32, SENT32) if dtype == torch.float32 else (torch.int16, SENT16)
-    flat = torch.full((n + 2 * PAD,), sent, dtype=it, device=dev)
-    return flat, flat[PAD:PAD + n].view(dtype).view(shape)
+    flat = torch.full((n + 2 * pad,), sent, dtype=it, device=dev)
+    return flat, flat[pad:pad + n].view(dtype).view(shape)
 
 
-def guards_intact(flat, n):
+def guards_intact(flat, n, pad=PAD):
     sent = SENT32 if flat.dtype == torch.int32 else SENT16
-    return bool((flat[:PAD] == sent).all()) and bool((flat[PAD + n:] == sent).all())
+    return bool((flat[:pad] == sent).all()) and bool((flat[pad + n:] == sent).all())
 
 
 def with_tail(t, dev, code=None):
