@@ -601,9 +601,10 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def quantize_weights(self, kind: str = "fp8", quantized_only: bool = False) -> bool:
         """Weight-only quantization for decode batches <= 64 (Req 10.3): per dense
-        layer, copies of the QKV / O / gate_up / down weights (after the RMSNorm
-        folding) as fp8 (E4M3, per-channel scale), int8 (per-channel scale) or int4
-        (per 128-k group scales), run by gemm_w8. Prefill and larger batches keep
+        layer, copies of the QKV / O / gate_up / down weights (unfolded:
+        build_model keeps the RMSNorm weights in the norms of a quantized model)
+        as fp8 (E4M3, per-channel scale), int8 (per-channel scale) or int4 (per
+        128-k group scales), run by gemm_w8. Prefill and larger batches keep
         the bf16 weights (MFMA-bound there); the fused bf16 decode layer is
         disabled. Returns False (and changes nothing) when a shape has no gemm_w8
         plan or the model is MoE (Mixtral experts have no quantized form).

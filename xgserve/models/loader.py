@@ -43,8 +43,13 @@ def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = N
         load_checkpoint(m, checkpoint)
     else:
         m.random_init(seed)
-    if hasattr(m, "fold_norms"):
-        m.fold_norms()  # RMSNorm weights into the projections (fused decode layer)
+    if hasattr(m, "fold_norms") and weight_dtype not in ("fp8", "int8", "int4"):
+        # RMSNorm weights into the projections (fused decode layer). Not for quantized weights:
+        # they never run the fused layer (norms_folded stays False, their norms keep their
+        # weights), and a norm weight with outliers folded into W sets every row's quantization
+        # scale: with entries 8x the rest, int8 logits were 4x further from the unquantized
+        # model's. Under random_init the norms are 1 and either order gives the same weights.
+        m.fold_norms()
     if weight_dtype in ("fp8", "int8", "int4"):
         if not (hasattr(m, "quantize_weights") and m.quantize_weights(weight_dtype, quantized_only=quantized_only)):
             raise ValueError(f"{weight_dtype} weights are not supported for {cfg.name} on {device}")
