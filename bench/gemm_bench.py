@@ -56,6 +56,9 @@ def main():
                     help="sweep gemm_m64g (nw, split, cfg) configurations instead of the shoot-out")
     ap.add_argument("--mw-sweep", action="store_true",
                     help="sweep gemm_mw (split, cfg) configurations at 64 < M <= 320 against hipBLASLt")
+    ap.add_argument("--mw8-sweep", action="store_true",
+                    help="gemm_mw8 (split, cfg) per shape, format and M against dequant_w8 + hipBLASLt and bf16 gemm_mw")
+    ap.add_argument("--formats", nargs="+", default=["fp8", "int8", "int4"], help="--mw8-sweep: weight formats")
     ap.add_argument("--top", type=int, default=6, help="--mw-sweep: configurations printed per (shape, M)")
     ap.add_argument("--splits", type=int, nargs="+", default=[1, 2, 3, 4, 5, 6, 8],
                     help="--m64g-sweep: split-K values of the partial-sum mode")
@@ -67,6 +70,8 @@ def main():
         return mw_sweep(a)
     if a.w8_sweep:
         return w8_sweep(a)
+    if a.mw8_sweep:
+        return mw8_sweep(a)
     if a.moe_sweep:
         return moe_sweep(a)
     dev = "cuda"
@@ -271,6 +276,90 @@ def mw_sweep(a):
                 fn = lambda w: L.m64_linear(x, w, mode)  # noqa: E731
                 show("m64g(plan)", timeit([lambda w=w: fn(w) for w in ws]), None)
         del ws
+        torch.cuda.empty_cache()
+
+
+def graph_us(fns, replays=10, rounds=3):
+    """us per call of each candidate in `fns` ({name: [zero-arg callables, one per cold weight copy]}): one
+    pass over the copies captured as a graph per candidate, replayed `replays` times per round; the
+    candidates alternate within a round. Returns {name: (median us, (max - min) / median over the rounds)}."""
+    graphs = {}
+    for name, calls in fns.items():
+        for c in calls[:2]:
+            c()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for c in calls:
+                c()
+        g.replay()
+        graphs[name] = (g, len(calls))
+    torch.cuda.synchronize()
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, (g, n) in graphs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(replays):
+                g.replay()
+            e.record()
+            torch.cuda.synchronize()
+            times[name].append(s.elapsed_time(e) / (replays * n) * 1000.0)
+    return {name: (sorted(t)[len(t) // 2], (max(t) - min(t)) / sorted(t)[len(t) // 2]) for name, t in times.items()}
+
+
+def mw8_sweep(a):
+    """gemm_mw8 at 64 < M <= 320: every (split, cfg) the kernel takes per (shape, format, M), cold weights,
+    graph-timed, beside the two paths it replaces, measured in the same process and alternating with it:
+    dequant_w8 into a scratch + hipBLASLt (+ silu_and_mul for gate_up: the quantized-only "dq" step) and
+    bf16 gemm_mw on its plan (the resident step). Every candidate is checked against fp32 first."""
+    from xgserve import ops
+    k = kernels()
+    st = torch.cuda.current_stream().cuda_stream
+    for name in a.shapes:
+        N, K = SHAPES[name]
+        mode = L.MODE_SILU if name.startswith("gate_up") and not name.endswith("_p") else L.MODE_PARTIAL
+        copies = max(2, min(8, (1 << 30) // (N * K * 2) + 1))
+        ws = [(torch.randn(N, K, device="cuda") * 0.02).bfloat16() for _ in range(copies)]
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device="cuda")
+        for kind in a.formats:
+            fmt = L.WQ_FORMATS[kind]
+            qs = [L.quantize_weight(w, fmt) for w in ws]
+            wd = L.dequantize_weight(*qs[0], fmt)
+            for M in a.M:
+                x = torch.randn(M, K, device="cuda").bfloat16()
+                y = x.float() @ wd.t()
+                if mode == L.MODE_SILU:
+                    g, u = L.deinterleave_gate_up(y.t().contiguous())
+                    y = F.silu(g.t()) * u.t()
+
+                def dq(q, sc):
+                    o = F.linear(x, L.dequantize_into(q, sc, fmt, out=scratch))
+                    return ops.silu_and_mul(o, interleave16=True) if mode == L.MODE_SILU else o
+                fns = {"dq+lib": [lambda q=q, sc=sc: dq(q, sc) for q, sc in qs]}
+                if L.mw_plan(M, N, K, mode) is not None:
+                    fns["mw_bf16"] = [lambda w=w: L.mw_linear(x, w, mode) for w in ws]
+                plan = L.mw8_plan(M, N, K, mode, fmt)
+                for cfg, (cols, _, _) in L.MW8_CFGS.items():
+                    for S in ((1,) if mode != L.MODE_PARTIAL else (1, 2, 3, 4, 5, 6, 8, 12, 16)):
+                        if not k.mw8_supports(M, K, N, S, mode, cfg, fmt) or (S > 1 and (N // cols) * S > 640):
+                            continue
+                        got = L.mw8_linear(x, *qs[0], mode, plan=(S, cfg), fmt=fmt)
+                        got = got.part.sum(0) if mode == L.MODE_PARTIAL else got.float()
+                        err = float((got - y).norm() / y.norm())
+                        assert err < 1e-2, (name, kind, M, S, cfg, err)
+                        fns[f"mw8(S={S},cfg={cfg})"] = [lambda q=q, sc=sc, S=S, cfg=cfg: L.mw8_linear(
+                            x, q, sc, mode, plan=(S, cfg), fmt=fmt) for q, sc in qs]
+                res = graph_us(fns)
+                best = sorted((v, n) for n, v in res.items() if n.startswith("mw8"))[:a.top]
+                keep = ["dq+lib", "mw_bf16"] + [n for _, n in best] + ([f"mw8(S={plan[0]},cfg={plan[1]})"] if plan else [])
+                for n in dict.fromkeys(keep):
+                    if n in res:
+                        print(json.dumps({"shape": name, "fmt": kind, "M": M, "op": n, "us": round(res[n][0], 2),
+                                          "spread": round(res[n][1], 3), "default_plan": plan is not None and
+                                          n == f"mw8(S={plan[0]},cfg={plan[1]})"}), flush=True)
+            del qs
+        del ws, scratch
         torch.cuda.empty_cache()
 
 

@@ -1,5 +1,5 @@
 // Host side of the hand-written GEMM families (gemm_m64g.hip dense and grouped,
-// gemm_w8.hip, gemm_mw.hip, gemm_pf.hip dense and grouped): the one declaration of their
+// gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped): the one declaration of their
 // entry points, of the row type of each family's configuration table (the table itself
 // sits next to its kernel) and of the no-launch shape predicates, shared by the kernels'
 // translation units and the pybind11 layer (ops.cpp).
@@ -31,6 +31,10 @@ struct MwCfg {
   bool nt;
   constexpr int cols() const { return 16 * wn * nwt; }
 };
+struct Mw8Cfg {
+  int wn, nwt, dw;  // waves along N (8 / wn along M), 16-column tiles per wave, code ring slots
+  constexpr int cols() const { return 16 * wn * nwt; }
+};
 struct PfCfg {
   int bm, mtp, lag;  // tile rows, 16-row m tiles per wave per phase, DMA lag (phases)
   bool grouped;      // also a cfg of gemm_pf_grouped
@@ -38,6 +42,7 @@ struct PfCfg {
 int m64g_cfgs(const M64Cfg** rows);
 int w8_cfgs(const W8Cfg** rows);
 int mw_cfgs(const MwCfg** rows);
+int mw8_cfgs(const Mw8Cfg** rows);
 int pf_cfgs(const PfCfg** rows);
 
 constexpr int M64G_MAX_M = 64, W8_MAX_M = 64, MW_MAX_M = 320;
@@ -49,6 +54,7 @@ bool m64g_supports(int M, int K, int N, int S, int mode, int nw, int cfg);
 bool moe_m64g_supports(int E, int K, int N, int P, int S, int mode, int nw, int cfg, int max_rows);
 bool w8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
 bool mw_supports(int M, int K, int N, int S, int mode, int cfg);
+bool mw8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
 bool pf_supports(int M, int K, int N, int S, int mode, int cfg);
 bool pf_grouped_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg);
 
@@ -86,6 +92,11 @@ int gemm_w8(const uint16_t* x, int M, int K, const uint8_t* w, const float* scal
             int S, int mode, int cfg, hipStream_t st, int fmt);
 int gemm_mw(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S, int mode,
             int cfg, hipStream_t st);
+// gemm_mw8.hip: gemm_mw's range, epilogues and split-K contract on fp8 / int8 / int4 codes
+// (fmt WQ_*: the layouts gemm_w8 reads); bytes of LDS a (cfg, M, fmt) needs, 0 = does not fit
+int gemm_mw8(const uint16_t* x, int M, int K, const uint8_t* w, const float* scale, int N, float* part, uint16_t* out,
+             int S, int mode, int cfg, int fmt, hipStream_t st);
+int mw8_lds_bytes(int M, int cfg, int fmt);
 int gemm_pf(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S, int mode,
             int cfg, hipStream_t st);
 int gemm_pf_grouped(const uint16_t* x, const int32_t* rows, const int32_t* offs, int E, int P, int K,

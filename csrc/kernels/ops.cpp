@@ -444,6 +444,14 @@ PYBIND11_MODULE(_kernels, m) {
                        S(st)),
           "gemm_mw");
   });
+  // gemm_mw's range on fp8 / int8 / int4 codes (gemm_mw8.hip)
+  m.def("gemm_mw8", [](uintptr_t x, int M, int K, uintptr_t w, uintptr_t scale, int N, uintptr_t part, uintptr_t out,
+                       int splits, int mode, int cfg, int fmt, uintptr_t st) {
+    check(xgk::gemm_mw8(P<const uint16_t>(x), M, K, P<const uint8_t>(w), P<const float>(scale), N, P<float>(part),
+                        P<uint16_t>(out), splits, mode, cfg, fmt, S(st)),
+          "gemm_mw8");
+  });
+  m.def("mw8_lds_bytes", &xgk::mw8_lds_bytes);
   // prompt-sized MFMA GEMM (gemm_pf.hip): mixed steps above gemm_mw's range, prefill
   m.def("gemm_pf", [](uintptr_t x, int M, int K, uintptr_t w, int N, uintptr_t part, uintptr_t out, int splits,
                       int mode, int cfg, uintptr_t st) {
@@ -498,6 +506,10 @@ PYBIND11_MODULE(_kernels, m) {
     for (int i = 0, n = xgk::mw_cfgs(&mw); i < n; ++i)
       lmw.append(py::make_tuple(mw[i].cols(), mw[i].d, mw[i].nt));
     d["mw"] = lmw;
+    const xgk::Mw8Cfg* mw8;
+    py::list lmw8;
+    for (int i = 0, n = xgk::mw8_cfgs(&mw8); i < n; ++i) lmw8.append(py::make_tuple(mw8[i].cols(), mw8[i].dw, mw8[i].wn));
+    d["mw8"] = lmw8;
     const xgk::PfCfg* pf;
     py::list lpf;
     for (int i = 0, n = xgk::pf_cfgs(&pf); i < n; ++i)
@@ -514,6 +526,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("moe_m64g_supports", &xgk::moe_m64g_supports);
   m.def("w8_supports", &xgk::w8_supports);
   m.def("mw_supports", &xgk::mw_supports);
+  m.def("mw8_supports", &xgk::mw8_supports);
   m.def("pf_supports", &xgk::pf_supports);
   m.def("pf_grouped_supports", &xgk::pf_grouped_supports);
   m.def("add_partials_resid", [](uintptr_t part, int S_, int T, uintptr_t res, uintptr_t ss_part, int H,

@@ -30,6 +30,29 @@ CSRC = ROOT / "csrc"
 BUILD = ROOT / "build" / "obj"
 EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 ARCH = os.environ.get("XGS_OFFLOAD_ARCH", "gfx950")
+# Per-source hipcc flags. gemm_mw8.hip is built without the packed fp32 instructions (v_pk_mul_f32 /
+# v_pk_fma_f32 / v_pk_add_f32): its column-scale multiply and int4 group fold are specified, and
+# tested bit for bit, as one plain fp32 operation per element. It is not about registers: without
+# the flag hipcc forms about 3,400 packed operations over the 55 instantiations, none of them
+# uses scratch either way, and 11 differ by 1-8 VGPRs. (cc1 of the host pass ignores the feature.)
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"gemm_mw8.hip": NO_PACKED_FP32}
+# Sources whose kernels must not spill: which instantiations exist is decided by a register rule
+# fitted to the compiler (gemm_mw8.hip mw8_regs), so the build reads the compiler's resource report
+# and fails on any scratch instead of trusting the rule.
+NO_SCRATCH = {"gemm_mw8.hip"}
+RESOURCE_REPORT = ["-Rpass-analysis=kernel-resource-usage"]
+
+
+def _check_no_scratch(src: Path, report: str) -> None:
+    import re
+    sizes = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", report)]
+    if not sizes:
+        raise RuntimeError(f"{src.name}: hipcc's resource report ({' '.join(RESOURCE_REPORT)}) has no ScratchSize "
+                           f"line, so the no-scratch rule of this file cannot be checked")
+    if any(sizes):
+        raise RuntimeError(f"{src.name}: {sum(1 for v in sizes if v)} of {len(sizes)} kernels use scratch "
+                           f"(up to {max(sizes, default=0)} B per lane); no kernel of this file may spill")
 
 
 def _pybind_includes() -> list:
@@ -104,7 +127,7 @@ def build_kernels(force: bool = False, jobs: int = 8, probes: bool = False) -> P
     out = PKG / f"_kernels{EXT}"
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden",
              "-munsafe-fp-atomics", "-Wno-unused-result"] + (["-DXGK_PROBES=1"] if probes else [])
-    stamp = _digest(srcs + hdrs + cpp, flags)
+    stamp = _digest(srcs + hdrs + cpp, flags + [f"{k}:{' '.join(v)}" for k, v in sorted(EXTRA_FLAGS.items())] + sorted(NO_SCRATCH))
     if not _needs(out, stamp, force):
         return out
     obj_dir = BUILD / "kernels"
@@ -113,7 +136,11 @@ def build_kernels(force: bool = False, jobs: int = 8, probes: bool = False) -> P
 
     def cc(src):
         o = obj_dir / (src.stem + ".o")
-        _run(["hipcc", *flags, *inc, "-c", str(src), "-o", str(o)])
+        check = src.name in NO_SCRATCH
+        log = _run(["hipcc", *flags, *EXTRA_FLAGS.get(src.name, []), *(RESOURCE_REPORT if check else []), *inc, "-c",
+                    str(src), "-o", str(o)])
+        if check:
+            _check_no_scratch(src, log)
         return o
 
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:

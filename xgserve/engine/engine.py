@@ -126,6 +126,7 @@ class EngineConfig:
     # released (their bytes go to the KV pool) and steps above 64 rows dequantize one
     # projection at a time into a shared scratch (LlamaForCausalLM.quantize_weights)
     quantized_only: bool = False
+    mw8: bool = True                  # quantized models: 65..320-row steps on gemm_mw8 where it measured ahead
     # custom xGMI all-reduce peer-wait limit while serving: a TP peer this late fails
     # the step (CustomAllReduceTimeout -> replica restart); warmup runs under 20 s
     collective_timeout_s: float = 2.0
@@ -154,7 +155,7 @@ class LLMEngine:
         self.model = model if model is not None else build_model(self.mcfg, device=device, dtype=dtype,
                                                                  checkpoint=cfg.checkpoint, seed=cfg.seed,
                                                                  weight_dtype=cfg.weight_dtype,
-                                                                 quantized_only=cfg.quantized_only)
+                                                                 quantized_only=cfg.quantized_only, mw8=cfg.mw8)
         self.model.set_moe_comm(cfg.moe_comm)
         # static after load: resident weight bytes (parameters + quantized copies) and the
         # quantized-only dequantization scratch, reported by stats()

@@ -424,7 +424,7 @@ class ModelRunner:
                         dec_block_tables=self.m_bt[:nb], dec_seq_lens=self.m_sl[:nb],
                         num_splits=self.decode_splits(nb), workspace=self.workspace,
                         pre_block_tables=self.m_bt[B:B + 1], pre_qsl=self.m_qsl, pre_seq_lens=self.m_sl[B:B + 1],
-                        pre_max_q=C)
+                        pre_max_q=C, mixed_graph=True)
         h = self.model(ids_t, meta, self.kv_caches)
         logits = self.model.compute_logits(h.index_select(0, self.m_lidx[:nb + 1]))
         return self._sample_rows(logits, nb + 1, greedy, proc)

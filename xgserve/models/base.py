@@ -31,6 +31,7 @@ class AttnMeta:
     pre_qsl: Optional[torch.Tensor] = None
     pre_seq_lens: Optional[torch.Tensor] = None
     pre_max_q: int = 0
+    mixed_graph: bool = False   # a body of the runner's mixed-step graphs: its GEMM families stay as they were
 
     @property
     def num_prefill_tokens(self) -> int:

@@ -25,7 +25,10 @@ or gemm_m64g up to 64 tokens (skinny_gemm up to 16 where gemm_m64g has no small-
 plan), gemm_mw up to 320, gemm_pf inside its measured windows, else the library.
 A quantized-only model (quantize_weights(kind, quantized_only=True)) has no bf16
 projection weights: above 64 tokens each projection is dequantized (dequant.hip)
-into one shared bf16 scratch that the library GEMM reads.
+into one shared bf16 scratch that the library GEMM reads, except that its steps of
+65..320 tokens run the projections that have a gemm_mw8 plan on the codes themselves
+("mw8": models quantized with mw8=True, as the engine does; a resident model too, where
+MW8_RESIDENT lists a measured shape).
 The HIP GEMMs hand split-K partials to their consumer (the attention prologue or
 add + RMSNorm) and gate inside gate_up; the library GEMMs are followed by rope_cache
 and silu_and_mul launches. Pure-decode steps of dense and MoE models normally take
@@ -48,7 +51,7 @@ from ..ops import linear as linear_mod
 from ..ops.linear import (MODE_BF16, MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M, W8_MIN_ELEMS, PendingSum,
                           ResidWorkspace, RowStats, dequantize_into, lm_head_linear, m64_ar_resid_linear,
                           m64_linear, m64_plan, m64_resid_linear,
-                          mw_linear, mw_plan, pf_linear, pf_plan,
+                          mw8_linear, mw8_plan, mw_linear, mw_plan, pf_linear, pf_plan,
                           quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
                           w8_plan, WQ_FORMATS)
 from .base import AttnMeta, PagedAttention, init_weight, kv_head_range, local_heads, shard
@@ -73,6 +76,23 @@ FUSED_DECODE = tune.get_bool("fused_decode", True)
 # MFMA GEMMs whose split-K partials go to the consumers, SiLU-gate in gate_up.
 # 0 = hipBLASLt for every step above 64 tokens.
 MW_MAX_TOKENS = min(MW_MAX_M, tune.get_int("mw_max_tokens", MW_MAX_M))
+# The same steps of a quantized model can read the fp8 / int8 / int4 codes on gemm_mw8
+# (csrc/kernels/gemm_mw8.hip) when the model was quantized with mw8=True (the engine's
+# default; quantize_weights' own default keeps the earlier steps), on TP = 1, in eager
+# steps and captured decode graphs (the runner's mixed-step graphs keep their families),
+# per projection, where mw8_plan has a plan at every row bucket and profiles/mw8.md measured it ahead of the path it replaces at every bucket:
+#   quantized-only (dequant_w8 + library GEMM): 1.2-4.4x ahead at every measured shape,
+#     format and bucket, so every projection with a plan takes it;
+#   resident (bf16 gemm_mw): only (shape, format) pairs that ran ahead at every bucket by more
+#     than the spread of their rows, in two runs: the Llama-3-70B projections in fp8 (9-30 %
+#     ahead on 256-column tiles, spreads up to 8 %). fp8 at the 8B shapes is within +-10 %,
+#     int8 ahead at some 70B buckets only, int4 10-30 % behind everywhere: those keep gemm_mw.
+# XGS_TUNE mw8=0 restores the earlier choice everywhere.
+MW8 = tune.get_bool("mw8", True)
+MW8_BUCKET_ENDS = (W8_MAX_M + 1, 128, 129, 192, 193, 256, 257, MW_MAX_M)  # both ends of every plan bucket
+# (N, K, fmt) of the projections of a resident model that take gemm_mw8
+MW8_RESIDENT = frozenset((N, K, linear_mod.WQ_FP8) for N, K in ((10240, 8192), (8192, 8192), (57344, 8192),
+                                                                (8192, 28672)))
 # Prompt-sized mixed steps on TP = 1: each projection takes gemm_pf
 # (csrc/kernels/gemm_pf.hip) for the step sizes where it measured faster than the
 # tuned library GEMM (profiles/r6/r6p_pf_vs_library.md, cold weights, the engine's
@@ -134,7 +154,7 @@ PROJECTIONS = ("qkv", "o", "gate_up", "down")
 
 class Step(NamedTuple):
     """The GEMM kernel family of each projection at one step -- "w8", "skinny", "m64",
-    "mw", "pf" (HIP: QKV / O / down as split-K partials into their consumers, the SiLU
+    "mw", "mw8", "pf" (HIP: QKV / O / down as split-K partials into their consumers, the SiLU
     gate inside gate_up), "lib" (library GEMM, bf16 out) or "dq" (the quantized weight
     dequantized into the model's scratch, then the library GEMM) -- and the attention entry:
     "fused_decode" / "from_partials" for QKV partials, "rope" for a QKV tensor. MoE
@@ -176,10 +196,13 @@ class LayerDispatch:
         self.attn_fq_ok = attn_fq_ok    # the decode attention kernel's fused-QKV form fits the head layout
         self.quantized: Optional[Step] = None
         self.dequantized: Optional[Step] = None  # T > W8_MAX_M of a model without its bf16 weights
+        self.mw8: Optional[Step] = None          # W8_MAX_M < T <= MW_MAX_TOKENS with a projection on gemm_mw8
+        self.on_gpu, self.tp = on_gpu, tp
         self.fast_ok = on_gpu and H % 256 == 0 and HqD % 256 == 0 and Nqkv % 64 == 0 and (moe or Fl % 256 == 0)
         shapes = ((Nqkv, H, MODE_PARTIAL), (H, HqD, MODE_PARTIAL))
         if not moe:
             shapes += ((2 * Fl, H, MODE_SILU), (H, Fl, MODE_PARTIAL))
+        self.shapes = dict(zip(PROJECTIONS, shapes))
         # M <= 16 on gemm_m64g too, when every projection has a measured small-M plan
         self.m64_small_ok = self.fast_ok and all(m64_plan(1, n, k, mode) is not None for n, k, mode in shapes)
         # 64 < M <= MW_MAX_TOKENS: gemm_mw for every projection (MoE layers: the attention
@@ -200,18 +223,39 @@ class LayerDispatch:
         return cls((Hq + 2 * Hkv) * D, cfg.hidden_size, Hq * D, 0 if moe else cfg.intermediate_size // tp, moe, tp,
                    on_gpu, attn_fq_ok)
 
-    def set_quantized(self, names, resident: bool = True) -> None:
+    def set_quantized(self, names, resident: bool = True, fmt: Optional[int] = None) -> None:
         """The projections in `names` have fp8 / int8 / int4 copies (gemm_w8, T <= W8_MAX_M);
         the others run their bf16 weight on gemm_m64g there. resident=False: the bf16
         weights of `names` are gone, so every larger step dequantizes them into the
         model's scratch for the library GEMM ("dq") -- no bf16 HIP GEMM family is ever
-        chosen for them."""
+        chosen for them. fmt (WQ_*, the format of the copies; TP = 1 only): steps
+        of W8_MAX_M < T <= MW_MAX_TOKENS run each projection of `names` that has a gemm_mw8
+        plan at every row bucket and was measured ahead there (a resident model:
+        MW8_RESIDENT) on its codes ("mw8"); the other projections keep that step's family of
+        today. Without fmt, or when no projection qualifies, nothing changes."""
         self.quantized = Step(*("w8" if n in names else "m64" for n in PROJECTIONS), "from_partials")
         self.dequantized = None if resident else Step(*("dq" if n in names else "lib" for n in PROJECTIONS), "rope")
+        self.mw8 = None
+        if fmt is None or not (MW8 and self.on_gpu and self.tp == 1 and MW_MAX_TOKENS > W8_MAX_M):
+            return
+        today = self.select(W8_MAX_M + 1, 0)  # (the same step up to MW_MAX_TOKENS: MW, LIB or dequantized)
+        fam = []
+        for n in PROJECTIONS:
+            N, K, mode = self.shapes.get(n, (0, 0, 0))
+            take = (N, K, fmt) in MW8_RESIDENT if resident else True
+            ok = (n in names and n in self.shapes and take
+                  and all(mw8_plan(T, N, K, mode, fmt) is not None for T in MW8_BUCKET_ENDS if T <= MW_MAX_TOKENS))
+            fam.append("mw8" if ok else getattr(today, n))
+        if "mw8" in fam:
+            self.mw8 = Step(*fam, "from_partials" if fam[0] in ("mw8", "mw") else "rope")
 
-    def select(self, T: int, num_decodes: int) -> Step:
+    def select(self, T: int, num_decodes: int, mixed_graph: bool = False) -> Step:
+        """mixed_graph: a body of the runner's mixed-step graphs (AttnMeta.mixed_graph), which keep
+        the families they had: no "mw8". Decode graphs and eager steps take it."""
         if self.quantized is not None and T <= W8_MAX_M:
             return self.quantized
+        if self.mw8 is not None and T <= MW_MAX_TOKENS and not mixed_graph:
+            return self.mw8
         if self.dequantized is not None:
             return self.dequantized
         if self.fast_ok and T <= FAST_M_SLAB:
@@ -291,6 +335,9 @@ class LlamaLayer(nn.Module):
         if family == "w8":
             q = self.w8[name]
             return w8_linear(x, q[0], q[1], mode, fmt=q[2])
+        if family == "mw8":
+            q = self.w8[name]
+            return mw8_linear(x, q[0], q[1], mode, fmt=q[2])
         if family == "dq":
             # One scratch for every projection of every layer: the whole step runs on one
             # stream, so the GEMM that reads the scratch is enqueued before the next
@@ -427,7 +474,7 @@ class LlamaLayer(nn.Module):
         else:
             h, residual = ops.fused_add_rmsnorm(x, residual, self.input_norm, eps)
         T = meta.num_tokens
-        step = self.dispatch.select(T, meta.num_decodes)
+        step = self.dispatch.select(T, meta.num_decodes, mixed_graph=meta.mixed_graph)
         qkv = self._gemm(step.qkv, h, "qkv", MODE_PARTIAL)
         if step.attn == "fused_decode":
             a = self.attn.fused_decode(qkv, meta, kv, cos_sin)
@@ -599,22 +646,28 @@ class LlamaForCausalLM(nn.Module):
         return self.quantize_weights("fp8")
 
     @torch.no_grad()
-    def quantize_weights(self, kind: str = "fp8", quantized_only: bool = False) -> bool:
+    def quantize_weights(self, kind: str = "fp8", quantized_only: bool = False, mw8: bool = False) -> bool:
         """Weight-only quantization for decode batches <= 64 (Req 10.3): per dense
         layer, copies of the QKV / O / gate_up / down weights (unfolded:
         build_model keeps the RMSNorm weights in the norms of a quantized model)
         as fp8 (E4M3, per-channel scale), int8 (per-channel scale) or int4 (per
-        128-k group scales), run by gemm_w8. Prefill and larger batches keep
-        the bf16 weights (MFMA-bound there); the fused bf16 decode layer is
-        disabled. Returns False (and changes nothing) when a shape has no gemm_w8
+        128-k group scales), run by gemm_w8. mw8=True (what the engine passes,
+        EngineConfig.mw8): steps of 65..MW_MAX_TOKENS rows on TP = 1 (not the runner's
+        mixed-step graphs) read the
+        same codes on gemm_mw8, per projection, where mw8_plan has a plan at every
+        row bucket (checked here, once) and it was measured ahead (a resident model:
+        MW8_RESIDENT); a model without such a projection, and mw8=False, behave as
+        before.
+        Larger steps keep the bf16 weights (MFMA-bound there); the fused bf16
+        decode layer is disabled. Returns False (and changes nothing) when a shape has no gemm_w8
         plan or the model is MoE (Mixtral experts have no quantized form).
 
         quantized_only: the model is served from the quantized weights alone. Layer
         by layer, once a layer's copies exist the bf16 storage of its quantized
         projections is released (peak: the bf16 model plus about one layer), and
-        steps above 64 rows dequantize one projection at a time into one model-wide
-        bf16 scratch of the largest projection that the library GEMM reads
-        (LayerDispatch "dq"). The freed bytes go back to the device, where the
+        steps above 64 rows that are not gemm_mw8's dequantize one projection at a
+        time into one model-wide bf16 scratch of the largest projection that the
+        library GEMM reads (LayerDispatch "dq"). The freed bytes go back to the device, where the
         engine's KV-pool sizing finds them."""
         fmt = WQ_FORMATS[kind]
         if self.device.type != "cuda" or any(l.moe for l in self.layers):
@@ -634,7 +687,7 @@ class LlamaForCausalLM(nn.Module):
         chosen = [n for n in names if use_q(n)]
         for l in self.layers:
             l.w8 = {n: quantize_weight(getattr(l, n), fmt) + (fmt,) for n in chosen}
-            l.dispatch.set_quantized(chosen, resident=not quantized_only)
+            l.dispatch.set_quantized(chosen, resident=not quantized_only, fmt=fmt if mw8 else None)
             if quantized_only:
                 for n in chosen:
                     l.released[n] = tuple(getattr(l, n).shape)

@@ -29,11 +29,14 @@ def model_class(cfg: ModelConfig):
 
 def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = None,
                 checkpoint: Optional[str] = None, seed: int = 0, tp: Optional[int] = None,
-                rank: Optional[int] = None, weight_dtype: Optional[str] = None, quantized_only: bool = False):
+                rank: Optional[int] = None, weight_dtype: Optional[str] = None, quantized_only: bool = False,
+                mw8: bool = False):
     """weight_dtype "fp8" / "int8" / "int4": also keep quantized weight copies for
     decode batches <= 64 (LlamaForCausalLM.quantize_weights); activations and
     everything else stay `dtype`. quantized_only: keep ONLY the quantized projection
-    weights (the bf16 originals are released; larger steps dequantize into a scratch)."""
+    weights (the bf16 originals are released; larger steps dequantize into a scratch).
+    mw8: 65..320-row steps of the quantized model read the codes on gemm_mw8
+    (LlamaForCausalLM.quantize_weights)."""
     if quantized_only and weight_dtype not in ("fp8", "int8", "int4"):
         raise ValueError(f"quantized_only needs weight_dtype fp8 / int8 / int4, got {weight_dtype!r}")
     if dtype is None:
@@ -51,7 +54,8 @@ def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = N
         # model's. Under random_init the norms are 1 and either order gives the same weights.
         m.fold_norms()
     if weight_dtype in ("fp8", "int8", "int4"):
-        if not (hasattr(m, "quantize_weights") and m.quantize_weights(weight_dtype, quantized_only=quantized_only)):
+        if not (hasattr(m, "quantize_weights")
+                and m.quantize_weights(weight_dtype, quantized_only=quantized_only, mw8=mw8)):
             raise ValueError(f"{weight_dtype} weights are not supported for {cfg.name} on {device}")
     elif weight_dtype not in (None, "bf16", "fp16", "fp32"):
         raise ValueError(f"unknown weight_dtype {weight_dtype!r}")

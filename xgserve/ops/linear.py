@@ -1,8 +1,8 @@
 """The projections' HIP GEMMs, one wrapper and one planner per kernel: skinny_gemm
 (M <= 16 register streaming), gemm_m64g (M <= 64, with the fused decode layer's
 row-scale / residual / all-reduce epilogues), gemm_mw (64 < M <= 320), gemm_pf
-(prompt-sized M), gemm_w8 (fp8 / int8 / int4 weights, M <= 64), and the split-K
-library GEMM for prefill-sized down projections.
+(prompt-sized M), gemm_w8 (fp8 / int8 / int4 weights, M <= 64), gemm_mw8 (the same
+weights, 64 < M <= 320), and the split-K library GEMM for prefill-sized down projections.
 
 `PendingSum` is a value that exists only as fp32 split-K partial sums; the
 kernels that consume it (add_partials_rmsnorm, rope_cache_partials) reduce it
@@ -832,4 +832,113 @@ def w8_linear(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, mode: int =
     res, part, outp = _result(x, M, N, S, mode, out)
     kernels().gemm_w8(x.data_ptr(), M, K, q.data_ptr(), scale.data_ptr(), N, part, outp, S, mode, cfg, stream_ptr(),
                       fmt)
+    return res
+
+
+# ---------------------------------------------------------------------------- gemm_mw8 (codes, 64 < M <= 320)
+# csrc/kernels/gemm_mw8.hip: gemm_mw's workgroup (a column tile x every row of x, split-K partials,
+# bf16 and SiLU epilogues) streaming the fp8 / int8 / int4 codes themselves, widened in registers.
+# cfg -> (columns per workgroup, code ring slots, waves along N), the mirror of MW8_CFGS there.
+MW8_CFGS = {0: (128, 3, 4), 1: (128, 2, 4), 2: (256, 2, 4), 3: (128, 2, 2)}
+MW8_DX_MAX, MW8_MAX_REGS = 5, 200
+
+
+def mw8_chunk(fmt: int) -> int:
+    """k per code chunk: one 128-B LDS row of codes per column."""
+    return 256 if fmt == WQ_INT4 else 128
+
+
+def _mw8_lds(M: int, cfg: int, fmt: int) -> int:
+    """LDS bytes of (cfg, M, fmt), 0 when it does not exist: `slots` code slots of 128 B per column
+    (int4: + the chunk's two scale rows), and the x ring of 64-k sub-chunks (128 B per row of M
+    rounded up to 64) in what is left of the 160 KB, at most 5 and at least 2 slots; the wave's
+    accumulator and fragment registers (int4: twice, for the group accumulators) stay within 200."""
+    if not (1 <= M <= MW_MAX_M) or cfg not in MW8_CFGS or fmt not in (WQ_FP8, WQ_INT8, WQ_INT4):
+        return 0
+    cols, slots, wn = MW8_CFGS[cfg]
+    xt, i4 = -(-M // 64), fmt == WQ_INT4
+    wbytes = slots * (cols * 128 + (8 * cols if i4 else 0))
+    dx = min(MW8_DX_MAX, (160 * 1024 - wbytes) // (64 * xt * 128))
+    nwt, mtw, k = cols // (16 * wn), 4 * xt // (8 // wn), 2 if i4 else 1
+    if dx < 2 or 4 * (nwt * mtw * k + mtw * k) > MW8_MAX_REGS:
+        return 0
+    return wbytes + dx * 64 * xt * 128
+
+
+def _mw8_fits(M: int, cfg: int, fmt: int) -> bool:
+    return _mw8_lds(M, cfg, fmt) > 0
+
+
+def _mw8_valid(M: int, N: int, K: int, mode: int, S: int, cfg: int, fmt: int) -> bool:
+    """gemm_mw8.hip mw8_supports: whole code chunks (int4: two whole groups each, so no split cuts
+    a group), whole column tiles, the rings in the LDS; bf16 / SiLU epilogues at split 1."""
+    if not _mw8_fits(M, cfg, fmt) or S < 1 or N < 1 or K < 1:
+        return False
+    kc = mw8_chunk(fmt)
+    if K % kc or S > K // kc or N % MW8_CFGS[cfg][0]:
+        return False
+    return mode == MODE_PARTIAL or (mode in (MODE_BF16, MODE_SILU) and S == 1)
+
+
+# (N, K, mode, fmt) -> {M bucket (128 / 192 / 256 / 320): (split_k, cfg)}: the fastest measured plan
+# where it ran more than 3 % ahead of the default rule's (bench/gemm_bench.py --mw8-sweep, cold weights,
+# graph-timed: profiles/mw8.md; "a vs b us" = this plan vs the default one); the rest take the default
+_MW8_TUNED = {
+    (6144, 4096, MODE_PARTIAL, WQ_INT4): {128: (8, 2), 192: (5, 1), 256: (5, 3)},  # qkv: 21 vs 23, 27 vs 28, 30 vs 32 us
+    (4096, 4096, MODE_PARTIAL, WQ_INT4): {128: (8, 1)},  # o: 15 vs 16 us
+    (28672, 4096, MODE_SILU, WQ_FP8): {128: (1, 1), 320: (1, 3)},  # gate_up: 51 vs 52, 79 vs 81 us
+    (28672, 4096, MODE_SILU, WQ_INT4): {128: (1, 1), 192: (1, 1), 256: (1, 3)},  # gate_up: 64 vs 71, 78 vs 86, 90 vs 94 us
+    (4096, 14336, MODE_PARTIAL, WQ_FP8): {128: (16, 2)},  # down: 26 vs 27 us
+    (4096, 14336, MODE_PARTIAL, WQ_INT8): {128: (16, 2), 192: (16, 2)},  # down: 29 vs 32, 35 vs 37 us
+    (4096, 14336, MODE_PARTIAL, WQ_INT4): {128: (16, 2), 256: (8, 3)},  # down: 32 vs 35, 47 vs 48 us
+    (10240, 8192, MODE_PARTIAL, WQ_FP8): {128: (6, 2), 192: (6, 2), 256: (6, 2), 320: (6, 2)},  # qkv70: 33 vs 35, 40 vs 45, 48 vs 54, 55 vs 61 us
+    (10240, 8192, MODE_PARTIAL, WQ_INT8): {128: (6, 2), 192: (6, 2), 256: (6, 2), 320: (6, 2)},  # qkv70: 39 vs 45, 45 vs 52, 53 vs 59, 60 vs 66 us
+    (10240, 8192, MODE_PARTIAL, WQ_INT4): {128: (6, 2)},  # qkv70: 41 vs 50 us
+    (8192, 8192, MODE_PARTIAL, WQ_FP8): {128: (8, 2), 192: (8, 2), 256: (8, 2), 320: (8, 2)},  # o70: 27 vs 29, 33 vs 36, 39 vs 42, 45 vs 48 us
+    (8192, 8192, MODE_PARTIAL, WQ_INT8): {128: (8, 2), 192: (8, 2), 256: (8, 2), 320: (8, 2)},  # o70: 32 vs 35, 37 vs 40, 43 vs 46, 49 vs 52 us
+    (8192, 8192, MODE_PARTIAL, WQ_INT4): {128: (8, 2), 256: (4, 3)},  # o70: 32 vs 39, 53 vs 55 us
+    (57344, 8192, MODE_SILU, WQ_FP8): {128: (1, 2), 192: (1, 2), 256: (1, 2), 320: (1, 2)},  # gate_up70: 142 vs 183, 168 vs 228, 211 vs 264, 251 vs 323 us
+    (57344, 8192, MODE_SILU, WQ_INT8): {128: (1, 2), 192: (1, 2), 256: (1, 2), 320: (1, 2)},  # gate_up70: 173 vs 240, 201 vs 267, 238 vs 291, 278 vs 349 us
+    (57344, 8192, MODE_SILU, WQ_INT4): {128: (1, 2), 192: (1, 1), 256: (1, 3)},  # gate_up70: 177 vs 269, 297 vs 322, 341 vs 368 us
+    (8192, 28672, MODE_PARTIAL, WQ_FP8): {128: (8, 2), 192: (8, 2), 256: (8, 2), 320: (8, 2)},  # down70: 71 vs 82, 87 vs 105, 105 vs 127, 121 vs 146 us
+    (8192, 28672, MODE_PARTIAL, WQ_INT8): {128: (8, 2), 192: (8, 2), 256: (8, 2), 320: (8, 2)},  # down70: 86 vs 106, 99 vs 123, 117 vs 141, 133 vs 159 us
+    (8192, 28672, MODE_PARTIAL, WQ_INT4): {128: (8, 2), 256: (4, 3)},  # down70: 85 vs 113, 160 vs 167 us
+}
+
+
+@functools.lru_cache(maxsize=None)  # (pure; an eager mixed step asks once per projection)
+def mw8_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, fmt: int = WQ_FP8):
+    """(split_k, cfg) for gemm_mw8, or None when the shape is unsupported. Default: 128-column
+    tiles on the deepest code ring that still leaves three x slots (cfg 0 up to 192 rows, then
+    cfg 1; int4 above 256 rows: cfg 3, the layout whose accumulators fit the registers there);
+    split-K (PARTIAL only) to the split nearest 256 workgroups, as mw_plan."""
+    if not (1 <= M <= MW_MAX_M) or fmt not in (WQ_FP8, WQ_INT8, WQ_INT4) or K % mw8_chunk(fmt):
+        return None
+    t = _MW8_TUNED.get((N, K, mode, fmt), {}).get(_mw_bucket(M))
+    if t is None or not _mw8_valid(M, N, K, mode, t[0], t[1], fmt):  # (a tuned plan that does not take this M)
+        cfg = 0 if M <= 192 else (3 if fmt == WQ_INT4 and M > 256 else 1)
+        cols = MW8_CFGS[cfg][0]
+        if N % cols:
+            return None
+        S = max(1, min(K // mw8_chunk(fmt), round(256 / (N // cols)))) if mode == MODE_PARTIAL else 1
+        t = (S, cfg)
+    return t if _mw8_valid(M, N, K, mode, t[0], t[1], fmt) else None
+
+
+def mw8_linear(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, mode: int = MODE_PARTIAL, plan=None,
+               out: Optional[torch.Tensor] = None, fmt: int = WQ_FP8):
+    """gemm_mw8 for 1 <= M <= 320 on the quantized weight (q, scale) of quantize_weight(w, fmt):
+    PendingSum (MODE_PARTIAL), bf16 [M, N] (MODE_BF16) or silu(gate) * up [M, N / 2] of a block-16
+    interleaved gate|up weight (MODE_SILU) -- what mw_linear returns for the dequantized weight."""
+    M, K, N = _operands("gemm_mw8", x, q, mode, out, w_dtype=torch.uint8, int4=fmt == WQ_INT4)
+    p = plan or (mw8_plan(M, N, K, mode, fmt) if fmt in (WQ_FP8, WQ_INT8, WQ_INT4) else None)
+    if (p is None or scale.dtype != torch.float32 or not scale.is_contiguous() or scale.device != x.device
+            or mode not in (MODE_BF16, MODE_PARTIAL, MODE_SILU)
+            or scale.numel() != (N * (K // WQ_GROUP) if fmt == WQ_INT4 else N)
+            or not _mw8_valid(M, N, K, mode, p[0], p[1], fmt)):
+        raise ValueError(f"gemm_mw8: unsupported M={M} N={N} K={K} mode={mode} fmt={fmt} plan={p}")
+    S, cfg = p
+    res, part, outp = _result(x, M, N, S, mode, out)
+    kernels().gemm_mw8(x.data_ptr(), M, K, q.data_ptr(), scale.data_ptr(), N, part, outp, S, mode, cfg, fmt,
+                       stream_ptr())
     return res

@@ -18,6 +18,8 @@ Keys (default in brackets; every default is the production setting):
   krot [1]                 K-chunk rotation of the weight-streaming GEMMs (0 / 1 / 2)
   m64_plans / mw_plans     gemm_m64g / gemm_mw plan overrides, "NxKxMODE@BUCKET=...;..."
   mw_max_tokens [320]      largest step on gemm_mw
+  mw8 [1]                  65..320-row steps of a quantized model read the codes on gemm_mw8 (0: bf16 gemm_mw
+                           of a resident model, dequantize + library GEMM of a quantized-only one)
   resid_inlaunch_kb [32]   in-launch residual reduce bound of the fused decode GEMMs
   decode_depth [2]         decode attention K/V register pipeline depth (4: depth 2 with the classic QKV prologue)
   decode_max_splits [16]   split-K cap of decode attention
@@ -40,7 +42,7 @@ import os
 from typing import Dict
 
 KEYS = {"fused_decode", "async_sched", "early_release", "spin_wait", "pf", "pf_windows", "moe_pf", "moe_w2_small", "argmax_split", "gemm_ar", "gemm_ar_shared", "small_m_tiles", "krot", "m64_plans", "mw_plans",
-        "mw_max_tokens", "resid_inlaunch_kb", "decode_depth", "decode_max_splits", "mixed_attn", "ar_ll_max", "sim_ar_us",
+        "mw_max_tokens", "mw8", "resid_inlaunch_kb", "decode_depth", "decode_max_splits", "mixed_attn", "ar_ll_max", "sim_ar_us",
         "tp_overlap_chunks", "tp_overlap_min_tokens", "ep_exact_min_pairs"}
 
 
