@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES))
     ap.add_argument("--moe-sweep", action="store_true",
                     help="sweep the grouped (MoE) gemm_m64g configurations at Mixtral decode shapes")
+    ap.add_argument("--moe-w8-sweep", action="store_true",
+                    help="the grouped GEMM on expert codes (moe_gemm_w8): every cfg / w2 split / format at Mixtral "
+                         "decode steps of --M tokens, beside the bf16 grouped kernel")
     ap.add_argument("--w8-sweep", action="store_true",
                     help="every gemm_w8 (fp8 weight) configuration per shape at M <= 16, cold weights")
     ap.add_argument("--m64g-sweep", action="store_true",
@@ -74,6 +77,8 @@ def main():
         return mw8_sweep(a)
     if a.moe_sweep:
         return moe_sweep(a)
+    if a.moe_w8_sweep:
+        return moe_w8_sweep(a)
     dev = "cuda"
     for name in a.shapes:
         N, K = SHAPES[name]
@@ -409,6 +414,69 @@ def moe_sweep(a):
             for us, nw, S, cfg in sorted((r[1], r[2], r[3], r[4]) for r in res if r[0] == name)[:8]:
                 print(json.dumps({"moe": name, "T": T, "P": P, "nw": nw, "S": S, "cfg": cfg, "us": round(us, 2)}),
                       flush=True)
+
+
+def moe_w8_sweep(a):
+    """Mixtral-8x7B expert GEMMs on fp8 / int8 / int4 codes (moe_gemm_w8) at decode steps of a.M
+    tokens (top-2 of 8, random routing): every configuration and w2 split the kernel takes, cold
+    weights (copies of all experts, enough that a step's active experts exceed the Infinity Cache
+    over one cycle), beside the bf16 grouped gemm_m64g on moe_m64_plan's choice at the same T in
+    the same run. `plan` marks moe_w8_plan's choice."""
+    from xgserve.ops import moe as MO
+    k = kernels()
+    E, H, F = 8, 4096, 14336
+    st = torch.cuda.current_stream().cuda_stream
+    base = {"w13": (torch.randn(E, 2 * F, H, device="cuda") * 0.02).bfloat16(),
+            "w2": (torch.randn(E, H, F, device="cuda") * 0.02).bfloat16()}
+    shape = {"w13": (2 * F, H), "w2": (H, F)}
+
+    def ring(t, active_bytes):  # copies of t: 2 active experts x copies >= 512 MB
+        return [t] + [t.clone() for _ in range(max(2, min(8, -(-(512 << 20) // active_bytes))) - 1)]
+    bf = {n: ring(w, 2 * w[0].numel() * 2) for n, w in base.items()}
+    for kind in a.formats:
+        fmt = L.WQ_FORMATS[kind]
+        qs = {}
+        for n, w in base.items():
+            q, sc = L.quantize_expert_stack(w, fmt)
+            qs[n] = [(c, sc) for c in ring(q, 2 * q[0].numel())]
+        for T in a.M:
+            pairs = 2 * T
+            g = torch.Generator(device="cuda").manual_seed(T)
+            ids = torch.stack([torch.randperm(E, generator=g, device="cuda")[:2] for _ in range(T)]).int()
+            x = torch.randn(T, H, device="cuda").bfloat16()
+            rows, offs, _ = MO.moe_align(ids, E, 0)
+            P = rows.shape[0]
+            act = torch.randn(P, F, device="cuda").bfloat16()
+            cfg13, nw2, cfg2, S2 = MO.moe_m64_plan(pairs, E, H, F)
+            part = torch.empty(16, P, H, dtype=torch.float32, device="cuda")
+            out = torch.empty(P, F, dtype=torch.bfloat16, device="cuda")
+            plan = MO.moe_w8_plan(pairs, E, H, F, fmt)
+            res = {"w13": [], "w2": []}
+            res["w13"].append((timeit([lambda w=w: k.moe_gemm_m64g_rows(
+                x.data_ptr(), rows.data_ptr(), offs.data_ptr(), E, H, w.data_ptr(), 2 * F, P, 0, out.data_ptr(), 1, 2, 2,
+                cfg13, pairs, st, rows.data_ptr(), pairs) for w in bf["w13"]]), "bf16", cfg13, 1))
+            res["w2"].append((timeit([lambda w=w: k.moe_gemm_m64g_rows(
+                act.data_ptr(), 0, offs.data_ptr(), E, F, w.data_ptr(), H, P, part.data_ptr(), 0, S2, 1, nw2, cfg2,
+                pairs, st, rows.data_ptr(), pairs) for w in bf["w2"]]), "bf16", cfg2, S2))
+            for which, mode, xin, xrows, (N, K) in (("w13", L.MODE_SILU, x, rows.data_ptr(), shape["w13"]),
+                                                    ("w2", L.MODE_PARTIAL, act, 0, shape["w2"])):
+                for cfg in MO.MOE_W8_GEOM:
+                    for S in ((1,) if which == "w13" else MO.MOE_W8_SPLITS):  # (what moe_combine reduces)
+                        if not k.moe_w8_supports(E, K, N, P, S, mode, cfg, fmt, pairs):
+                            continue
+                        us = timeit([lambda q=q, sc=sc, cfg=cfg, S=S: k.moe_gemm_w8(
+                            xin.data_ptr(), xrows, offs.data_ptr(), E, K, q.data_ptr(), sc.data_ptr(), N, P,
+                            part.data_ptr() if mode == L.MODE_PARTIAL else 0, 0 if mode == L.MODE_PARTIAL else out.data_ptr(),
+                            S, mode, cfg, fmt, pairs, st, rows.data_ptr(), pairs) for q, sc in qs[which]])
+                        res[which].append((us, kind, cfg, S))
+            for which, rs in res.items():
+                chosen = (plan[0], 1) if which == "w13" else (plan[1], plan[2])
+                best = sorted(r for r in rs if r[1] != "bf16")[:a.top]
+                for us, fm, cfg, S in [rs[0]] + best + [r for r in rs if r[1] != "bf16" and r[2:] == chosen and r not in best]:
+                    print(json.dumps({"moe_w8": which, "fmt": fm, "T": T, "P": P, "cfg": cfg, "S": S, "us": round(us, 2),
+                                      "plan": fm != "bf16" and (cfg, S) == chosen}), flush=True)
+        del qs
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":

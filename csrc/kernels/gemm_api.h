@@ -1,5 +1,5 @@
 // Host side of the hand-written GEMM families (gemm_m64g.hip dense and grouped,
-// gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped): the one declaration of their
+// gemm_w8.hip, moe_gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped): the one declaration of their
 // entry points, of the row type of each family's configuration table (the table itself
 // sits next to its kernel) and of the no-launch shape predicates, shared by the kernels'
 // translation units and the pybind11 layer (ops.cpp).
@@ -41,6 +41,7 @@ struct PfCfg {
 };
 int m64g_cfgs(const M64Cfg** rows);
 int w8_cfgs(const W8Cfg** rows);
+int moe_w8_cfgs(const W8Cfg** rows);
 int mw_cfgs(const MwCfg** rows);
 int mw8_cfgs(const Mw8Cfg** rows);
 int pf_cfgs(const PfCfg** rows);
@@ -53,6 +54,7 @@ constexpr int WQ_SC_FLOATS = 4096;  // int4 scales staged per workgroup (groups 
 bool m64g_supports(int M, int K, int N, int S, int mode, int nw, int cfg);
 bool moe_m64g_supports(int E, int K, int N, int P, int S, int mode, int nw, int cfg, int max_rows);
 bool w8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
+bool moe_w8_supports(int E, int K, int N, int P, int S, int mode, int cfg, int fmt, int max_rows);
 bool mw_supports(int M, int K, int N, int S, int mode, int cfg);
 bool mw8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
 bool pf_supports(int M, int K, int N, int S, int mode, int cfg);
@@ -90,6 +92,11 @@ void set_k_rotation(int mode);
 int k_rotation(int S);  // gemm_m64g.hip; gemm_mw follows the same policy
 int gemm_w8(const uint16_t* x, int M, int K, const uint8_t* w, const float* scale, int N, float* part, uint16_t* out,
             int S, int mode, int cfg, hipStream_t st, int fmt);
+// moe_gemm_w8.hip: moe_gemm_m64g's layout operands on expert codes (fmt WQ_*: fp8 / int8 codes
+// [E, N, K] + scales [E, N]; int4 codes [E, N, K / 2] + group scales [E, K / 128, N])
+int moe_gemm_w8(const uint16_t* x, const int32_t* rows, const int32_t* offs, int E, int K, const uint8_t* w,
+                const float* scale, int N, int P, float* part, uint16_t* out, int S, int mode, int cfg, int fmt,
+                int max_rows, hipStream_t st, const int32_t* valid, int pairs = 0);
 int gemm_mw(const uint16_t* x, int M, int K, const uint16_t* w, int N, float* part, uint16_t* out, int S, int mode,
             int cfg, hipStream_t st);
 // gemm_mw8.hip: gemm_mw's range, epilogues and split-K contract on fp8 / int8 / int4 codes

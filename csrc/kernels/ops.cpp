@@ -501,6 +501,9 @@ PYBIND11_MODULE(_kernels, m) {
     py::list lw8;
     for (int i = 0, n = xgk::w8_cfgs(&w8); i < n; ++i) lw8.append(py::make_tuple(w8[i].nw, w8[i].wv, w8[i].kc));
     d["w8"] = lw8;
+    py::list lw8g;
+    for (int i = 0, n = xgk::moe_w8_cfgs(&w8); i < n; ++i) lw8g.append(py::make_tuple(w8[i].nw, w8[i].wv, w8[i].kc));
+    d["moe_w8"] = lw8g;
     const xgk::MwCfg* mw;
     py::list lmw;
     for (int i = 0, n = xgk::mw_cfgs(&mw); i < n; ++i)
@@ -525,6 +528,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("m64g_supports", &xgk::m64g_supports);
   m.def("moe_m64g_supports", &xgk::moe_m64g_supports);
   m.def("w8_supports", &xgk::w8_supports);
+  m.def("moe_w8_supports", &xgk::moe_w8_supports);
   m.def("mw_supports", &xgk::mw_supports);
   m.def("mw8_supports", &xgk::mw8_supports);
   m.def("pf_supports", &xgk::pf_supports);
@@ -602,6 +606,18 @@ PYBIND11_MODULE(_kernels, m) {
      py::arg("P"), py::arg("part"), py::arg("splits"), py::arg("nw"), py::arg("cfg"), py::arg("max_rows"),
      py::arg("st"), py::arg("valid"), py::arg("dest"), py::arg("wts"), py::arg("resid"), py::arg("ss_out"),
      py::arg("counters"), py::arg("T"), py::arg("k"), py::arg("pairs") = 0);
+  // the grouped GEMM on expert codes (moe_gemm_w8.hip): moe_gemm_m64g_rows' layout operands,
+  // w / scale in the per-expert layouts of gemm_w8 (fmt 0 fp8, 1 int8, 2 int4)
+  m.def("moe_gemm_w8", [](uintptr_t x, uintptr_t rows, uintptr_t offs, int E, int K, uintptr_t w, uintptr_t scale,
+                          int N, int P_, uintptr_t part, uintptr_t out, int splits, int mode, int cfg, int fmt,
+                          int max_rows, uintptr_t st, uintptr_t valid, int pairs) {
+    check(xgk::moe_gemm_w8(P<const uint16_t>(x), P<const int32_t>(rows), P<const int32_t>(offs), E, K,
+                           P<const uint8_t>(w), P<const float>(scale), N, P_, P<float>(part), P<uint16_t>(out),
+                           splits, mode, cfg, fmt, max_rows, S(st), P<const int32_t>(valid), pairs),
+          "moe_gemm_w8");
+  }, py::arg("x"), py::arg("rows"), py::arg("offs"), py::arg("E"), py::arg("K"), py::arg("w"), py::arg("scale"),
+     py::arg("N"), py::arg("P"), py::arg("part"), py::arg("out"), py::arg("splits"), py::arg("mode"), py::arg("cfg"),
+     py::arg("fmt"), py::arg("max_rows"), py::arg("st"), py::arg("valid") = 0, py::arg("pairs") = 0);
   m.def("moe_route", [](uintptr_t h, uintptr_t wr, int T, int H, int E, int k, int renorm, uintptr_t w, uintptr_t ids,
                         uintptr_t st, uintptr_t norm_w, float eps, uintptr_t hn, uintptr_t al_rows, uintptr_t al_offs,
                         uintptr_t al_dest, int al_E, int al_eoff, int al_bm) {

@@ -36,11 +36,11 @@ ARCH = os.environ.get("XGS_OFFLOAD_ARCH", "gfx950")
 # the flag hipcc forms about 3,400 packed operations over the 55 instantiations, none of them
 # uses scratch either way, and 11 differ by 1-8 VGPRs. (cc1 of the host pass ignores the feature.)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"gemm_mw8.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"gemm_mw8.hip": NO_PACKED_FP32, "moe_gemm_w8.hip": NO_PACKED_FP32}  # (the same rule: explicit fmaf fold)
 # Sources whose kernels must not spill: which instantiations exist is decided by a register rule
 # fitted to the compiler (gemm_mw8.hip mw8_regs), so the build reads the compiler's resource report
 # and fails on any scratch instead of trusting the rule.
-NO_SCRATCH = {"gemm_mw8.hip"}
+NO_SCRATCH = {"gemm_mw8.hip", "moe_gemm_w8.hip"}
 RESOURCE_REPORT = ["-Rpass-analysis=kernel-resource-usage"]
 
 

@@ -52,8 +52,9 @@ from ..ops.linear import (MODE_BF16, MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M
                           ResidWorkspace, RowStats, dequantize_into, lm_head_linear, m64_ar_resid_linear,
                           m64_linear, m64_plan, m64_resid_linear,
                           mw8_linear, mw8_plan, mw_linear, mw_plan, pf_linear, pf_plan,
-                          quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
+                          quantize_expert_stack, quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
                           w8_plan, WQ_FORMATS)
+from ..ops.moe import moe_w8_plan
 from .base import AttnMeta, PagedAttention, init_weight, kv_head_range, local_heads, shard
 from .config import ModelConfig
 
@@ -358,10 +359,12 @@ class LlamaLayer(nn.Module):
         return skinny_linear(x, w, None, mode)
 
     # ------------------------------------------------------------------ MoE
-    def _moe_allreduce(self, h: torch.Tensor) -> torch.Tensor:
+    def _moe_allreduce(self, h: torch.Tensor, codes: bool = False) -> torch.Tensor:
         w, ids = ops.moe_route(h, self.router, self.cfg.experts_per_token)
+        # codes: the step reads the experts' quantized copies on moe_gemm_w8
+        wq = self.w8["w13"][:2] + self.w8["w2"] if codes else None
         out = ops.fused_moe(h, self.w13, self.w2, w, ids, self.expert_offset,
-                              experts_total=self.router.shape[0])
+                              experts_total=self.router.shape[0], wq=wq)
         return self._ar(out)
 
     def _moe_alltoall(self, h: torch.Tensor) -> torch.Tensor:
@@ -459,11 +462,13 @@ class LlamaLayer(nn.Module):
         # the partial output is a fresh contiguous [T, H] bf16 tensor like h
         return not (h.shape[0] <= EP_AR_MAX_TOKENS and ar is not None and ar.can_run(h.contiguous()))
 
-    def mlp(self, h: torch.Tensor) -> torch.Tensor:
-        """The experts of a MoE layer (a dense layer's MLP is the tail of `forward`)."""
+    def mlp(self, h: torch.Tensor, codes: bool = False) -> torch.Tensor:
+        """The experts of a MoE layer (a dense layer's MLP is the tail of `forward`).
+        codes: the quantized step of a quantized model (TP = 1) -- the experts run on their
+        fp8 / int8 / int4 copies."""
         if self.tp > 1 and self._moe_use_alltoall(h):
             return self._moe_alltoall(h)
-        return self._moe_allreduce(h)
+        return self._moe_allreduce(h, codes)
 
     def forward(self, x, residual: Optional[torch.Tensor], meta: AttnMeta,
                 kv: Tuple[torch.Tensor, torch.Tensor], cos_sin: torch.Tensor):
@@ -488,7 +493,8 @@ class LlamaLayer(nn.Module):
         o = self._ar(self._gemm(step.o, a, "o", MODE_PARTIAL))
         h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
         if self.moe:
-            return self.mlp(h), residual
+            # the experts switch to their codes where the attention projections do
+            return self.mlp(h, codes=step is self.dispatch.quantized and "w13" in (self.w8 or {})), residual
         if step.gate_up in ("lib", "dq"):  # bf16 gate|up rows out of the library GEMM
             act = ops.silu_and_mul(self._gemm(step.gate_up, h, "gate_up", MODE_BF16), interleave16=True)
         else:
@@ -660,7 +666,15 @@ class LlamaForCausalLM(nn.Module):
         before.
         Larger steps keep the bf16 weights (MFMA-bound there); the fused bf16
         decode layer is disabled. Returns False (and changes nothing) when a shape has no gemm_w8
-        plan or the model is MoE (Mixtral experts have no quantized form).
+        plan.
+
+        A MoE model (Mixtral) on TP = 1: QKV / O as above, and per layer quantized copies of
+        the expert stacks w13 / w2 (linear.quantize_expert_stack, counted by weight_bytes).
+        Steps of at most 64 tokens -- where LayerDispatch.select returns the quantized step
+        -- run the experts on the codes (moe_gemm_w8 through fused_moe(wq=...)); larger
+        steps read the resident bf16 experts as before. Returns False for a MoE model
+        under TP / EP, with quantized_only (the bf16 experts cannot be released: prompt
+        steps read them), or whose expert shapes have no moe_w8_plan.
 
         quantized_only: the model is served from the quantized weights alone. Layer
         by layer, once a layer's copies exist the bf16 storage of its quantized
@@ -670,10 +684,16 @@ class LlamaForCausalLM(nn.Module):
         library GEMM reads (LayerDispatch "dq"). The freed bytes go back to the device, where the
         engine's KV-pool sizing finds them."""
         fmt = WQ_FORMATS[kind]
-        if self.device.type != "cuda" or any(l.moe for l in self.layers):
-            return False
         l0 = self.layers[0]
-        names = ("qkv", "o", "gate_up", "down")
+        moe = any(l.moe for l in self.layers)
+        if self.device.type != "cuda" or (moe and (self.tp != 1 or quantized_only)):
+            return False
+        if moe:  # the experts at both ends of every row body and at the largest quantized step
+            E, F2, H = l0.w13.shape
+            k = self.cfg.experts_per_token
+            if any(moe_w8_plan(p, E, H, F2 // 2, fmt) is None for p in (1, 16, 17, W8_MAX_M * k)):
+                return False
+        names = ("qkv", "o") if moe else ("qkv", "o", "gate_up", "down")
         for n in names:
             w = getattr(l0, n)
             mode = MODE_SILU if n == "gate_up" else MODE_PARTIAL
@@ -687,6 +707,8 @@ class LlamaForCausalLM(nn.Module):
         chosen = [n for n in names if use_q(n)]
         for l in self.layers:
             l.w8 = {n: quantize_weight(getattr(l, n), fmt) + (fmt,) for n in chosen}
+            if l.moe:  # expert copies beside the resident bf16 experts (which larger steps read)
+                l.w8.update({n: quantize_expert_stack(getattr(l, n), fmt) + (fmt,) for n in ("w13", "w2")})
             l.dispatch.set_quantized(chosen, resident=not quantized_only, fmt=fmt if mw8 else None)
             if quantized_only:
                 for n in chosen:

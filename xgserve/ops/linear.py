@@ -740,6 +740,18 @@ def dequantize_weight(q: torch.Tensor, scale: torch.Tensor, fmt: int) -> torch.T
     return {WQ_FP8: dequantize_fp8, WQ_INT8: dequantize_int8, WQ_INT4: dequantize_int4}[fmt](q, scale)
 
 
+def quantize_expert_stack(w: torch.Tensor, fmt: int):
+    """An expert stack [E, N, K] -> (codes, scales), each expert's matrix quantized on its own
+    by quantize_weight and stacked: fp8 / int8 codes uint8 [E, N, K] + scales [E, N]; int4
+    codes [E, N, K / 2] + group scales [E, K / 128, N] (what moe_gemm_w8 reads;
+    dequantize_weight(codes[e], scales[e], fmt) is expert e's matrix). One expert at a time:
+    the fp32 temporaries stay one matrix large."""
+    if w.dim() != 3:
+        raise ValueError(f"quantize_expert_stack: expected [E, N, K], got {tuple(w.shape)}")
+    qs = [quantize_weight(w[e], fmt) for e in range(w.shape[0])]
+    return torch.stack([q for q, _ in qs]).contiguous(), torch.stack([s for _, s in qs]).contiguous()
+
+
 def dequantize_into(q: torch.Tensor, scale: torch.Tensor, fmt: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The bf16 weight [N, K] of quantized codes `q` (layouts of quantize_fp8 / _int8 /
     _int4), bit-identical to dequantize_weight(q, scale, fmt).to(bfloat16): one fp32

@@ -7,7 +7,7 @@ import torch
 
 from ._native import kernels, stream_ptr, use_native
 from .activation import silu_and_mul
-from .linear import M64G_CFGS
+from .linear import M64G_CFGS, MODE_PARTIAL, MODE_SILU, WQ_FP8, WQ_GROUP, WQ_INT4, WQ_INT8, WQ_SC_FLOATS
 
 BLOCK_M = 64
 # gemm_m64g launch configurations for the expert GEMMs (see ops/linear.py M64G_CFGS);
@@ -77,6 +77,49 @@ def moe_m64_plan(pairs: int, E: int, H: int, F: int):
         # workgroups on 256 CUs): 2 K splits fill the chip
         S = 2
     return cfg13, nw2, cfg2, S
+
+
+# ---------------------------------------------------------------------------- expert codes
+# csrc/kernels/moe_gemm_w8.hip: the grouped GEMMs of a decode-sized step on fp8 / int8 / int4
+# expert codes. cfg -> (16-column tiles per wave, waves per workgroup, k chunk), the mirror of
+# MOE_W8_CFGS there; the KC 256 rows have the 16-row body only (<= 16 pairs).
+MOE_W8_GEOM = {0: (2, 4, 128), 1: (2, 2, 128), 2: (1, 4, 128), 3: (2, 2, 256), 4: (2, 4, 256)}
+MOE_W8_SPLITS = (1, 2, 4)  # the slab counts moe_combine / moe_combine_resid reduce
+# fmt -> ((pairs up to, cfg of w13, cfg of w2, K splits of w2), ...), measured at the Mixtral-8x7B
+# expert shapes with bench/gemm_bench.py --moe-w8-sweep (profiles/moe_w8.md); other shapes and
+# int4 scale stages that do not fit start from the row and search (moe_w8_plan).
+_MOE_W8_TUNED = {
+    WQ_FP8: ((2, 0, 2, 4), (8, 0, 2, 2), (64, 0, 2, 1), (256, 0, 0, 2)),
+    WQ_INT8: ((2, 0, 2, 4), (8, 0, 2, 2), (64, 0, 2, 1), (256, 0, 2, 2)),
+    WQ_INT4: ((2, 0, 2, 4), (8, 0, 2, 2), (16, 0, 2, 4), (256, 0, 2, 2)),
+}
+
+
+def _moe_w8_fits(N: int, K: int, mode: int, S: int, cfg: int, max_rows: int, fmt: int) -> bool:
+    """The shape half of the library's moe_w8_supports (E and the layout size aside)."""
+    nw, wv, kc = MOE_W8_GEOM[cfg]
+    cols = 16 * nw * wv
+    if N % cols or K % (S * kc) or (max_rows > 16 and kc != 128) or (mode == MODE_SILU and (S != 1 or nw != 2)):
+        return False
+    return fmt != WQ_INT4 or ((K // S) % WQ_GROUP == 0 and (K // S // WQ_GROUP) * cols <= WQ_SC_FLOATS)
+
+
+def moe_w8_plan(pairs: int, E: int, H: int, F: int, fmt: int):
+    """moe_gemm_w8 configurations of a step's expert GEMMs on codes (pairs = token-expert
+    pairs <= MOE_PREFILL_PAIRS): (cfg of w13 [2F, H] with the SiLU gate, cfg of w2 [H, F], K
+    splits of w2), or None. The measured row for the pair count, kept where the kernel takes
+    it; otherwise the nearest configuration and the smallest larger split it does take
+    (int4 w2 at F = 14336: 112 groups x 64 columns of scales do not fit one stage, so the
+    split goes up)."""
+    if not 1 <= pairs <= MOE_PREFILL_PAIRS or fmt not in _MOE_W8_TUNED:
+        return None
+    _, c13, c2, S0 = next(r for r in _MOE_W8_TUNED[fmt] if pairs <= r[0])
+    cfg13 = next((c for c in (c13, 1, 0) if _moe_w8_fits(2 * F, H, MODE_SILU, 1, c, pairs, fmt)), None)
+    # the measured split, then the larger ones (smallest first), then the smaller ones
+    splits = [S0] + [s for s in MOE_W8_SPLITS if s > S0] + [s for s in reversed(MOE_W8_SPLITS) if s < S0]
+    w2 = next(((c, S) for c in (c2, 2, 1, 0) for S in splits if _moe_w8_fits(H, F, MODE_PARTIAL, S, c, pairs, fmt)),
+              None)
+    return None if cfg13 is None or w2 is None else (cfg13, w2[0], w2[1])
 
 
 def _moe_pf_ok(H: int, F: int) -> bool:
@@ -192,7 +235,7 @@ def moe_forward_ref(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w
 def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torch.Tensor,
               topk_ids: torch.Tensor, expert_offset: int = 0, resid: Optional[torch.Tensor] = None,
               ss: Optional[torch.Tensor] = None, out_f32: bool = False, layout=None,
-              counters: Optional[torch.Tensor] = None, experts_total: Optional[int] = None):
+              counters: Optional[torch.Tensor] = None, experts_total: Optional[int] = None, wq=None):
     """Local-expert MoE FFN: sum_j w_j * FFN_{e_j}(x) over choices owned locally
     (ids in [expert_offset, expert_offset + E_local)); others contribute nothing.
 
@@ -207,7 +250,12 @@ def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torc
     store into a column tile adds that tile's weighted rows into the residual), one
     launch fewer per layer; otherwise a separate combine kernel with 1024-column
     statistics. experts_total (EP shards): the global expert count, so the prompt-sized
-    path sizes its tiles by this rank's expected share of the pairs."""
+    path sizes its tiles by this rank's expected share of the pairs.
+    wq = (w13 codes, w13 scales, w2 codes, w2 scales, fmt) (linear.quantize_expert_stack of
+    w13 and w2): a step of at most MOE_PREFILL_PAIRS pairs on a GPU reads the codes
+    instead -- align -> moe_gemm_w8 on w13 (SiLU gate) -> moe_gemm_w8 on w2 (split-K
+    partials) -> the separate combine (no in-launch combine on codes); a shape without
+    a moe_w8_plan raises. Larger steps, and the CPU reference, read w13 / w2."""
     if not use_native(x):
         out = moe_forward_ref(x, w13, w2, topk_w, topk_ids, expert_offset)
         if resid is None:
@@ -227,6 +275,26 @@ def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torc
     kn = kernels()
     max_rows = T * k  # no expert holds more rows than (token, choice) pairs
     valid = sorted_rows.data_ptr()  # per-workgroup real-row count -> 16 / 32 / 64-row body
+
+    if wq is not None and max_rows <= MOE_PREFILL_PAIRS:
+        q13, s13, q2, s2, fmt = wq
+        plan = moe_w8_plan(max_rows, E, H, F, fmt)
+        kw = 2 if fmt == WQ_INT4 else 1  # codes per byte
+        if (plan is None or q13.dtype != torch.uint8 or q2.dtype != torch.uint8
+                or tuple(q13.shape) != (E, F2, H // kw) or tuple(q2.shape) != (E, H, F // kw)
+                or s13.dtype != torch.float32 or s2.dtype != torch.float32
+                or s13.numel() != E * F2 * (H // WQ_GROUP if fmt == WQ_INT4 else 1)
+                or s2.numel() != E * H * (F // WQ_GROUP if fmt == WQ_INT4 else 1)
+                or not all(t.is_contiguous() and t.device == x.device for t in (q13, s13, q2, s2))):
+            raise ValueError(f"moe_gemm_w8: unsupported experts E={E} H={H} F={F} fmt={fmt} pairs={max_rows}")
+        cfg13, cfg2, S = plan
+        kn.moe_gemm_w8(x.contiguous().data_ptr(), sorted_rows.data_ptr(), offs.data_ptr(), E, H, q13.data_ptr(),
+                       s13.data_ptr(), F2, P, 0, act.data_ptr(), 1, MODE_SILU, cfg13, fmt, max_rows, stream_ptr(),
+                       valid, T * k)
+        part = torch.empty(S, P, H, dtype=torch.float32, device=x.device)
+        kn.moe_gemm_w8(act.data_ptr(), 0, offs.data_ptr(), E, F, q2.data_ptr(), s2.data_ptr(), H, P, part.data_ptr(),
+                       0, S, MODE_PARTIAL, cfg2, fmt, max_rows, stream_ptr(), valid, T * k)
+        return _moe_combine(kn, part, S, P, dest, topk_w, resid, ss, T, k, H, x, out_f32)
 
     if MOE_PF and max_rows > MOE_PREFILL_PAIRS and _moe_pf_ok(H, F):
         share = max_rows * E // experts_total if experts_total else max_rows  # this rank's expected pairs
