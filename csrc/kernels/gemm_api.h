@@ -1,5 +1,5 @@
 // Host side of the hand-written GEMM families (gemm_m64g.hip dense and grouped,
-// gemm_w8.hip, moe_gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped): the one declaration of their
+// gemm_w8.hip, moe_gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped, gemm_f8.hip): the one declaration of their
 // entry points, of the row type of each family's configuration table (the table itself
 // sits next to its kernel) and of the no-launch shape predicates, shared by the kernels'
 // translation units and the pybind11 layer (ops.cpp).
@@ -39,12 +39,16 @@ struct PfCfg {
   int bm, mtp, lag;  // tile rows, 16-row m tiles per wave per phase, DMA lag (phases)
   bool grouped;      // also a cfg of gemm_pf_grouped
 };
+struct F8Cfg {
+  int bm, ns;  // tile rows, LDS ring slots (one 128-deep K tile of codes each)
+};
 int m64g_cfgs(const M64Cfg** rows);
 int w8_cfgs(const W8Cfg** rows);
 int moe_w8_cfgs(const W8Cfg** rows);
 int mw_cfgs(const MwCfg** rows);
 int mw8_cfgs(const Mw8Cfg** rows);
 int pf_cfgs(const PfCfg** rows);
+int f8_cfgs(const F8Cfg** rows);
 
 constexpr int M64G_MAX_M = 64, W8_MAX_M = 64, MW_MAX_M = 320;
 constexpr int WQ_GROUP = 128;       // k per int4 scale group
@@ -59,6 +63,7 @@ bool mw_supports(int M, int K, int N, int S, int mode, int cfg);
 bool mw8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
 bool pf_supports(int M, int K, int N, int S, int mode, int cfg);
 bool pf_grouped_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg);
+bool f8_supports(int M, int K, int N, int S, int mode, int cfg);
 
 // GG_MOE_RESID (grouped w2 of the fused decode layer, TP = 1): the MoE combine inside
 // the w2 launch. Every workgroup stores its fp32 partial rows write-through and takes a
@@ -110,5 +115,10 @@ int gemm_pf_grouped(const uint16_t* x, const int32_t* rows, const int32_t* offs,
                     const uint16_t* w, int N, int max_pairs, float* part, uint16_t* out, int S, int mode, int cfg,
                     hipStream_t st);
 void set_pf_krot(int on);
+// gemm_f8.hip: E4M3 codes on both sides (a [M, K] with row scales sx [M], w [N, K] with channel
+// scales sw [N]) on the K = 128 FP8 matrix instruction; quant_rows_fp8 makes (a, sx) from bf16 rows
+int gemm_f8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
+            uint16_t* out, int S, int mode, int cfg, hipStream_t st);
+int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
 
 }  // namespace xgk

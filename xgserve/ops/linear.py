@@ -954,3 +954,116 @@ def mw8_linear(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, mode: int 
     kernels().gemm_mw8(x.data_ptr(), M, K, q.data_ptr(), scale.data_ptr(), N, part, outp, S, mode, cfg, fmt,
                        stream_ptr())
     return res
+
+
+# ---------------------------------------------------------------------------- gemm_f8 (fp8 codes x fp8 codes, M > 320)
+# csrc/kernels/gemm_f8.hip: prompt-sized steps of an fp8 model on the FP8 matrix instructions. The
+# activations are quantized per row (token) to E4M3 with a dynamic scale, the weight codes are read
+# as quantize_fp8 stores them, and both scales are applied in the epilogue:
+#   out = diag(sx) (A . W^T) diag(sw)
+# cfg -> (tile rows, LDS ring slots), the mirror of F8_CFGS there; tiles are 256 columns wide.
+F8_CFGS = {0: (256, 2), 1: (128, 3)}
+F8_COLS, F8_KT = 256, 128
+F8_QUANT_MAX_K = 28672  # the row quantizer holds a row in registers
+_F8_TUNED = {}          # (N, K, mode) -> {M: (split_k, cfg)}: empty until somebody sweeps it
+
+
+def quantize_rows_fp8(x: torch.Tensor):
+    """[M, K] -> (uint8 E4M3 codes [M, K], fp32 per-row scales [M]): quantize_fp8 by rows, i.e. one
+    dynamic scale per token, sx = max(max|x_row| / 448, 1e-12). The definition that the HIP
+    quantizer (quant_rows_fp8) reproduces bit for bit, and the CPU path."""
+    return quantize_fp8(x)
+
+
+def quant_rows_fp8(x: torch.Tensor):
+    """quantize_rows_fp8 of a bf16 [M, K] on its device: the HIP kernel on a GPU, PyTorch elsewhere."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError(f"quant_rows_fp8: x must be a contiguous 2-d bfloat16, got {x.dtype} {tuple(x.shape)}")
+    M, K = x.shape
+    if not use_native(x):
+        return quantize_rows_fp8(x)
+    if M < 1 or K < 16 or K % 16 or K > F8_QUANT_MAX_K:
+        raise ValueError(f"quant_rows_fp8: needs M >= 1, K % 16 == 0, 16 <= K <= {F8_QUANT_MAX_K}, got M={M} K={K}")
+    codes = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    sx = torch.empty(M, dtype=torch.float32, device=x.device)
+    kernels().quant_rows_fp8(x.data_ptr(), M, K, codes.data_ptr(), sx.data_ptr(), stream_ptr())
+    return codes, sx
+
+
+def _f8_valid(M: int, N: int, K: int, mode: int, S: int, cfg: int) -> bool:
+    """gemm_f8.hip f8_supports: whole 256-column tiles, whole 128-k tiles, at least one K tile per
+    split; bf16 / SiLU epilogues at split 1."""
+    if M < 1 or cfg not in F8_CFGS:
+        return False
+    if K < F8_KT or K % F8_KT or N < F8_COLS or N % F8_COLS or S < 1 or S > K // F8_KT:
+        return False
+    if -(-M // F8_CFGS[cfg][0]) * (N // F8_COLS) * S >= 1 << 31:
+        return False
+    return mode == MODE_PARTIAL or (mode in (MODE_BF16, MODE_SILU) and S == 1)
+
+
+@functools.lru_cache(maxsize=4096)
+def f8_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
+    """(split_k, cfg) for gemm_f8, or None when the shape is unsupported. A rule, not a measured
+    table (_F8_TUNED is empty): the tile height that pads M least (ties: the taller tile); for
+    MODE_PARTIAL the smallest split-K that gives a full round of workgroups (one per CU), capped so
+    that every split keeps at least two K tiles; split 1 otherwise."""
+    if M < 1 or K % F8_KT or N % F8_COLS or K > F8_QUANT_MAX_K:
+        return None
+    t = _F8_TUNED.get((N, K, mode), {}).get(M)
+    if t is None:
+        cfg = min(F8_CFGS, key=lambda c: (-(-M // F8_CFGS[c][0]) * F8_CFGS[c][0], -F8_CFGS[c][0]))
+        S = 1
+        if mode == MODE_PARTIAL:
+            tiles = -(-M // F8_CFGS[cfg][0]) * (N // F8_COLS)
+            S = max(1, min(-(-cus // tiles), K // (2 * F8_KT)))
+        t = (S, cfg)
+    return t if _f8_valid(M, N, K, mode, t[0], t[1]) else None
+
+
+def f8_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MODE_PARTIAL,
+                    plan=None, out: Optional[torch.Tensor] = None):
+    """gemm_f8 on codes given: a [M, K] / q [N, K] uint8 E4M3, sx [M] / sw [N] fp32. Returns what
+    pf_linear returns for the dequantized operands: bf16 [M, N] (MODE_BF16), a PendingSum
+    (MODE_PARTIAL) or silu(gate) * up [M, N / 2] of a block-16 interleaved gate|up weight."""
+    def bad(what):
+        return ValueError(f"gemm_f8: {what}")
+
+    if a.dim() != 2 or q.dim() != 2 or a.dtype != torch.uint8 or q.dtype != torch.uint8:
+        raise bad(f"a and q must be 2-d uint8 codes, got {a.dtype} {tuple(a.shape)} and {q.dtype} {tuple(q.shape)}")
+    if sx.dtype != torch.float32 or sw.dtype != torch.float32:
+        raise bad(f"scales must be float32, got {sx.dtype} and {sw.dtype}")
+    if not (a.is_contiguous() and q.is_contiguous() and sx.is_contiguous() and sw.is_contiguous()):
+        raise bad("codes and scales must be contiguous")
+    if not (a.device == q.device == sx.device == sw.device) or not a.is_cuda:
+        raise bad("codes and scales must be on one GPU")
+    (M, K), N = a.shape, q.shape[0]
+    if q.shape[1] != K or sx.numel() != M or sw.numel() != N:
+        raise bad(f"a {tuple(a.shape)}, q {tuple(q.shape)}, {sx.numel()} row scales, {sw.numel()} channel scales")
+    if mode not in (MODE_BF16, MODE_PARTIAL, MODE_SILU):
+        raise bad(f"unknown mode {mode}")
+    if out is not None:
+        shape = (M, N // 2 if mode == MODE_SILU else N)
+        if (mode == MODE_PARTIAL or out.dtype != torch.bfloat16 or out.device != a.device
+                or not out.is_contiguous() or tuple(out.shape) != shape):
+            raise bad(f"out must be a contiguous bfloat16 {shape} on {a.device} (bf16 / SiLU modes only)")
+    p = plan or f8_plan(M, N, K, mode, cu_count(a.device))
+    if p is None or len(p) != 2 or not _f8_valid(M, N, K, mode, p[0], p[1]):
+        raise bad(f"unsupported M={M} N={N} K={K} mode={mode} plan={p}")
+    S, cfg = p
+    res, part, outp = _result(a, M, N, S, mode, out)
+    kernels().gemm_f8(a.data_ptr(), sx.data_ptr(), M, K, q.data_ptr(), sw.data_ptr(), N, part, outp, S, mode, cfg,
+                      stream_ptr())
+    return res
+
+
+def f8_linear(x: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MODE_PARTIAL, plan=None,
+              out: Optional[torch.Tensor] = None):
+    """x bf16 [M, K] quantized per row to E4M3 (quant_rows_fp8), then gemm_f8 against the fp8
+    weight (q, sw) of quantize_fp8: W8A8 with dynamic per-token scales."""
+    if x.dim() != 2 or q.dim() != 2 or x.shape[1] != q.shape[1] or not x.is_cuda or x.device != q.device:
+        raise ValueError(f"gemm_f8: x {tuple(x.shape)} on {x.device} does not go with q {tuple(q.shape)} on {q.device}")
+    if plan is None and f8_plan(x.shape[0], q.shape[0], x.shape[1], mode, cu_count(x.device)) is None:
+        raise ValueError(f"gemm_f8: unsupported M={x.shape[0]} N={q.shape[0]} K={x.shape[1]} mode={mode}")
+    a, sx = quant_rows_fp8(x)
+    return f8_linear_codes(a, sx, q, sw, mode, plan, out)

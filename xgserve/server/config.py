@@ -108,6 +108,10 @@ class WorkerSection:
     # a GPU; Mixtral experts are not covered)
     quantization: str = "bf16"
     quantized_only: bool = False
+    # with quantization fp8, tp 1, a dense model on a GPU: prompt steps above 320 rows quantize
+    # their activations per token to E4M3 and run on the FP8 matrix instructions (gemm_f8), so
+    # outputs differ from the weight-only server's; smaller steps stay weight-only
+    fp8_activations: bool = False
     block_size: int = 16
     max_num_seqs: int = 256
     max_num_batched_tokens: int = 8192
@@ -219,6 +223,20 @@ class ServerConfig:
             e.append(f"worker.quantized_only needs worker.quantization fp8|int8|int4, got {w.quantization!r}")
         if w.quantized_only and w.device == "cpu":
             e.append("worker.quantized_only needs a GPU (worker.device is cpu)")
+        if w.fp8_activations:
+            if w.quantization != "fp8":
+                e.append(f"worker.fp8_activations needs worker.quantization fp8, got {w.quantization!r}")
+            if w.device == "cpu":
+                e.append("worker.fp8_activations needs a GPU (worker.device is cpu)")
+            if w.tp != 1:
+                e.append(f"worker.fp8_activations needs worker.tp = 1, got {w.tp}")
+            if not w.mock:
+                try:
+                    from ..models.config import get_config
+                    if get_config(w.checkpoint or w.model).arch == "mixtral":
+                        e.append("worker.fp8_activations does not cover Mixtral (dense Llama models only)")
+                except Exception:  # (an unknown model is reported below)
+                    pass
         if not (0.0 < w.gpu_memory_utilization <= 1.0):
             e.append("worker.gpu_memory_utilization must be in (0, 1]")
         if w.block_size % 16:

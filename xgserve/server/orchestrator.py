@@ -1020,6 +1020,7 @@ class InferenceServer:
                          "memory_used": s["memory_used"], "memory_available": s["memory_available"],
                          "weight_bytes": st.get("weight_bytes", 0), "scratch_bytes": st.get("scratch_bytes", 0),
                          "weight_dtype": st.get("weight_dtype"),
+                         "activation_dtype": st.get("activation_dtype", "bf16"),
                          "kind": r.kind if r else None, "restarts": r.restarts if r else 0,
                          "requests_dispatched": self.dispatched.get(s["id"], 0),
                          "heartbeat_age_s": r.heartbeat_age() if r else None, "engine": st})
