@@ -7,7 +7,9 @@ gemm_bench.graph_us, the three candidates alternating within one call:
   bf16      pf_linear on its plan: today's resident prompt step
 
 One JSON line per (shape, M, op): us and achieved TFLOP/s from 2 M N K.
-  python bench/f8_bench.py [--shapes qkv o gate_up down ...] [--M 384 576 1024 2048 8192]"""
+--format int8: the same table for gemm_i8 (int8 weights, per-token int8 activations, INT8 matrix
+instructions) beside dequantize + library of the int8 weight and the same bf16 gemm_pf.
+  python bench/f8_bench.py [--format fp8|int8] [--shapes qkv o gate_up down ...] [--M 384 576 1024 2048 8192]"""
 import argparse
 import json
 import os
@@ -28,15 +30,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["qkv", "o", "gate_up", "down", "qkv70", "o70", "gate_up70", "down70"])
     ap.add_argument("--M", type=int, nargs="+", default=[384, 576, 1024, 2048, 8192])
+    ap.add_argument("--format", choices=["fp8", "int8"], default="fp8")
     a = ap.parse_args()
     kernels()
+    fam, fmt, quantize, dequantize, plan_of, linear, quant_rows = {
+        "fp8": ("f8", L.WQ_FP8, L.quantize_fp8, L.dequantize_fp8, L.f8_plan, L.f8_linear, L.quant_rows_fp8),
+        "int8": ("i8", L.WQ_INT8, L.quantize_int8, L.dequantize_int8, L.i8_plan, L.i8_linear, L.quant_rows_int8)}[a.format]
     for name in a.shapes:
         N, K = SHAPES[name]
         mode = L.MODE_SILU if name.startswith("gate_up") else L.MODE_PARTIAL
         copies = max(2, min(6, (1 << 30) // (N * K * 2) + 1))
         ws = [(torch.randn(N, K, device="cuda") * 0.02).bfloat16() for _ in range(copies)]
-        qs = [L.quantize_fp8(w) for w in ws]
-        wd = L.dequantize_fp8(*qs[0])
+        qs = [quantize(w) for w in ws]
+        wd = dequantize(*qs[0])
         scratch = torch.empty(N * K, dtype=torch.bfloat16, device="cuda")
         for M in a.M:
             x = torch.randn(M, K, device="cuda").bfloat16()
@@ -44,23 +50,23 @@ def main():
             if mode == L.MODE_SILU:
                 g, u = L.deinterleave_gate_up(y.t().contiguous())
                 y = F.silu(g.t()) * u.t()
-            plan = L.f8_plan(M, N, K, mode, L.cu_count())
-            got = L.f8_linear(x, *qs[0], mode)
+            plan = plan_of(M, N, K, mode, L.cu_count())
+            got = linear(x, *qs[0], mode)
             got = got.part.sum(0) if mode == L.MODE_PARTIAL else got.float()
             err = float((got - y).norm() / y.norm())
-            assert err < 0.1, (name, M, err)   # (E4M3 activations: a few percent)
+            assert err < 0.1, (name, M, err)   # (E4M3 activations: a few percent; int8: about one)
 
             def dq(q, sc):
-                o = F.linear(x, L.dequantize_into(q, sc, L.WQ_FP8, out=scratch))
+                o = F.linear(x, L.dequantize_into(q, sc, fmt, out=scratch))
                 return ops.silu_and_mul(o, interleave16=True) if mode == L.MODE_SILU else o
-            fns = {"f8": [lambda q=q, sc=sc: L.f8_linear(x, q, sc, mode) for q, sc in qs],
-                   "quant": [lambda: L.quant_rows_fp8(x) for _ in qs],
+            fns = {fam: [lambda q=q, sc=sc: linear(x, q, sc, mode) for q, sc in qs],
+                   "quant": [lambda: quant_rows(x) for _ in qs],
                    "dq+lib": [lambda q=q, sc=sc: dq(q, sc) for q, sc in qs],
                    "bf16": [lambda w=w: L.pf_linear(x, w, mode) for w in ws]}
             for op, (us, spread) in graph_us(fns).items():
                 print(json.dumps({"shape": name, "M": M, "op": op, "us": round(us, 2), "spread": round(spread, 3),
                                   "TFLOP/s": None if op == "quant" else round(2 * M * N * K / us / 1e6, 1),
-                                  "f8_plan": list(plan), "f8_rel_err": round(err, 4)}), flush=True)
+                                  f"{fam}_plan": list(plan), f"{fam}_rel_err": round(err, 4)}), flush=True)
         del ws, qs, scratch
         torch.cuda.empty_cache()
 

@@ -48,7 +48,7 @@ def bench_attn(L, Hq, Hkv, D, gh, iters=20, bs=16):
 
 
 def ttft(L, quantization=None, quantized_only=False, batch=0, batch_prompt_len=512, batch_out=64, default_graphs=False,
-         fp8_activations=False):
+         fp8_activations=False, int8_activations=False):
     from xgserve.engine import EngineConfig, LLMEngine, SamplingParams
     wdt = quantization if quantization in ("fp8", "int8", "int4") else None
     # default_graphs: the engine's own decode graph sizes (up to max_num_seqs; above 64 rows too)
@@ -56,7 +56,7 @@ def ttft(L, quantization=None, quantized_only=False, batch=0, batch_prompt_len=5
     eng = LLMEngine(EngineConfig(model="llama3-8b", max_num_seqs=max(4, batch), max_num_batched_tokens=max(8192, L),
                                  max_model_len=max(L, batch_prompt_len + batch_out) + 16, graph_batch_sizes=bs,
                                  weight_dtype=wdt, quantized_only=quantized_only,
-                                 fp8_activations=fp8_activations))
+                                 fp8_activations=fp8_activations, int8_activations=int8_activations))
     res = []
     for it in range(4):
         prompt = torch.randint(10, 128000, (L,)).tolist()
@@ -106,6 +106,10 @@ def main():
                     help="with --quantization fp8: prompt steps above 320 rows on gemm_f8 (activations quantized per token)")
     ap.add_argument("--fp8-activations-pair", action="store_true",
                     help="with --quantization fp8: the TTFT without and then with fp8 activations, in this one call")
+    ap.add_argument("--int8-activations", action="store_true",
+                    help="with --quantization int8: prompt steps above 320 rows on gemm_i8 (activations quantized per token)")
+    ap.add_argument("--int8-activations-pair", action="store_true",
+                    help="with --quantization int8: the TTFT without and then with int8 activations, in this one call")
     a = ap.parse_args()
     kernels()
     for name, Hq, Hkv in (("llama3-8b", 32, 8), ("llama3-70b", 64, 8)):
@@ -114,12 +118,15 @@ def main():
                 us, tf = bench_attn(L, Hq, Hkv, 128, gh)
                 print(json.dumps({"op": "prefill_attention", "heads": name, "L": L, "gh": gh, "us": round(us, 1),
                                   "TFLOP/s": round(tf, 1)}), flush=True)
-    for a8 in ([] if a.no_ttft else [False, True] if a.fp8_activations_pair else [a.fp8_activations]):
+    runs = ([(False, False), (True, False)] if a.fp8_activations_pair else
+            [(False, False), (False, True)] if a.int8_activations_pair else [(a.fp8_activations, a.int8_activations)])
+    for a8, ai8 in ([] if a.no_ttft else runs):
         r, extra = ttft(a.ttft_len, a.quantization, a.quantized_only, a.batch, a.batch_prompt_len, a.batch_out,
-                        a.default_graphs, a8)
+                        a.default_graphs, a8, ai8)
         torch.cuda.empty_cache()
         print(json.dumps({"op": "ttft_batch1", "model": "llama3-8b", "prompt_len": a.ttft_len,
                           "quantization": a.quantization, "quantized_only": a.quantized_only, "fp8_activations": a8,
+                          "int8_activations": ai8,
                           "ttft_ms": [round(x, 2) for x in r], "ttft_ms_best_of_last3": round(min(r[1:]), 2),
                           **extra}), flush=True)
 

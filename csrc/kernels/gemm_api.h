@@ -64,6 +64,7 @@ bool mw8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
 bool pf_supports(int M, int K, int N, int S, int mode, int cfg);
 bool pf_grouped_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg);
 bool f8_supports(int M, int K, int N, int S, int mode, int cfg);
+bool i8_supports(int M, int K, int N, int S, int mode, int cfg);  // f8_supports and K <= 131,072
 
 // GG_MOE_RESID (grouped w2 of the fused decode layer, TP = 1): the MoE combine inside
 // the w2 launch. Every workgroup stores its fp32 partial rows write-through and takes a
@@ -120,5 +121,10 @@ void set_pf_krot(int on);
 int gemm_f8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
             uint16_t* out, int S, int mode, int cfg, hipStream_t st);
 int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
+// the same kernel on int8 codes (w as quantize_int8 stores it) and v_mfma_i32_16x16x64_i8: int32 sums,
+// converted once per split; quant_rows_int8 makes (a, sx) with round-half-even codes in -127 .. 127
+int gemm_i8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
+            uint16_t* out, int S, int mode, int cfg, hipStream_t st);
+int quant_rows_int8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
 
 }  // namespace xgk

@@ -1,8 +1,20 @@
-// gemm_f8: prompt-sized GEMM (M > 320) of fp8 models on the FP8 matrix instructions, and the
-// row quantizer that makes its other operand:
+// gemm_f8 / gemm_i8: prompt-sized GEMM (M > 320) of fp8 and int8 models on the 8-bit matrix
+// instructions, and the row quantizers that make their other operand:
 //
 //   quant_rows_fp8:  x bf16 [M, K]  ->  codes E4M3 [M, K],  sx fp32 [M]
-//   gemm_f8:         out[M, N] = diag(sx) (A[M, K] . W[N, K]^T) diag(sw)
+//   quant_rows_int8: x bf16 [M, K]  ->  codes int8 [M, K],  sx fp32 [M]
+//   gemm_f8, gemm_i8: out[M, N] = diag(sx) (A[M, K] . W[N, K]^T) diag(sw)
+//
+// One kernel, two operand policies (F8Ops, I8Ops below): the byte images, the staging, the ring
+// and the epilogues do not depend on what a byte means. gemm_i8 reads int8 codes (W as
+// quantize_int8 stores it), accumulates in int32 on v_mfma_i32_16x16x64_i8 -- two instructions
+// per 32-B fragment, granule g (k 16g .. 16g + 15 of the low 64-k half) then granule g + 4 (the
+// same of the high half) -- and converts the integer sum once (v_cvt_f32_i32) before the scales.
+// |a w| <= 2^14 and the launcher refuses K > 131,072 = 2^17, so a whole-K sum stays inside int32;
+// a split converts its own sum, so a slab is float(sum_s) * sx * sw. quant_rows_int8 is
+// quant_rows_fp8 with sx = max(amax / 127, 1e-12) and code = clamp(rint(x / sx), -127, 127)
+// (v_rndne_f32: round half to even), bit-identical to quantize_rows_int8 of xgserve/ops/linear.py.
+// What follows describes gemm_f8; read "K = 128 instruction" as the instruction pair for int8.
 //
 // A and W are OCP E4M3 codes (W as quantize_fp8 stores it: [N, K] row-major, one fp32 scale per
 // output channel); the products are accumulated in fp32 by v_mfma_f32_16x16x128_f8f6f4 (the
@@ -95,14 +107,34 @@ static_assert(wait_count(2, 256) == 0 && wait_count(3, 128) == 6, "f8 wait count
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;   // operand of the K = 128 instruction
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 
-__device__ __forceinline__ f32x4_t mfma16x16x128_f8(i32x8_t a, i32x8_t b, f32x4_t c) {
+// Operand policies: the accumulator of one 16 x 16 tile, the product of one 32-B fragment pair
+// added to it, and the accumulator as a float.
+struct F8Ops {
+  using acc_t = f32x4_t;
+  static __device__ __forceinline__ acc_t mma(i32x8_t w, i32x8_t a, acc_t c) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  // formats 0 = E4M3 for both operands; scale arguments 0: the plain (unscaled) instruction
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
+    // formats 0 = E4M3 for both operands; scale arguments 0: the plain (unscaled) instruction
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, a, c, 0, 0, 0, 0, 0, 0);
 #else
-  return c;
+    return c;
 #endif
-}
+  }
+  static __device__ __forceinline__ float to_float(float v) { return v; }
+};
+struct I8Ops {
+  using acc_t = i32x4_t;
+  static __device__ __forceinline__ acc_t mma(i32x8_t w, i32x8_t a, acc_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the low 64 k (granule g) and the high 64 k (granule g + 4) of the fragment
+    c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_shufflevector(w, w, 0, 1, 2, 3),
+                                              __builtin_shufflevector(a, a, 0, 1, 2, 3), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_shufflevector(w, w, 4, 5, 6, 7),
+                                              __builtin_shufflevector(a, a, 4, 5, 6, 7), c, 0, 0, 0);
+#endif
+    return c;
+  }
+  static __device__ __forceinline__ float to_float(int v) { return static_cast<float>(v); }  // v_cvt_f32_i32
+};
 
 // 32 B of a fragment: granules c0 and c0 + 4 of an image row (already swizzled by the caller)
 __device__ __forceinline__ i32x8_t f8_frag(const uint8_t* row, int g, int sl) {
@@ -111,7 +143,7 @@ __device__ __forceinline__ i32x8_t f8_frag(const uint8_t* row, int g, int sl) {
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int BM, int NS, bool DB>
+template <class Ops, int BM, int NS, bool DB>
 __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restrict__ a, const float* __restrict__ sx,
                                                           int M, int K, const uint8_t* __restrict__ w,
                                                           const float* __restrict__ sw, int N, int S,
@@ -173,11 +205,11 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
              slot + ASZ + (4 * wid + i) * 1024);
   };
 
-  f32x4_t acc[MT][4];
+  typename Ops::acc_t acc[MT][4];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = typename Ops::acc_t{0, 0, 0, 0};
   auto w_frag = [&](int t, int nt) { return f8_frag(smem + (t % NS) * SLOT + ASZ + (wrow + 16 * nt + li) * 128, g, sl); };
   auto a_frag = [&](int t, int mt) { return f8_frag(smem + (t % NS) * SLOT + (arow + 16 * mt + li) * 128, g, sl); };
 
@@ -214,7 +246,7 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = mfma16x16x128_f8(fw[B][nt], fa[B][mt], acc[mt][nt]);
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = Ops::mma(fw[B][nt], fa[B][mt], acc[mt][nt]);
     };
     for (int t = 0; t < nk; t += 2) {
       step(t, std::integral_constant<int, 0>{});
@@ -241,7 +273,7 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
       for (int mt = 0; mt < MT; ++mt) {
         if (mt + 1 < MT) fa[(mt + 1) & 1] = a_frag(t, mt + 1);
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = mfma16x16x128_f8(fw[nt], fa[mt & 1], acc[mt][nt]);
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = Ops::mma(fw[nt], fa[mt & 1], acc[mt][nt]);
       }
     }
   }
@@ -260,10 +292,10 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
     float o[4][4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      o[nt][0] = acc[mt][nt][0] * rs * cs[nt].x;
-      o[nt][1] = acc[mt][nt][1] * rs * cs[nt].y;
-      o[nt][2] = acc[mt][nt][2] * rs * cs[nt].z;
-      o[nt][3] = acc[mt][nt][3] * rs * cs[nt].w;
+      o[nt][0] = Ops::to_float(acc[mt][nt][0]) * rs * cs[nt].x;
+      o[nt][1] = Ops::to_float(acc[mt][nt][1]) * rs * cs[nt].y;
+      o[nt][2] = Ops::to_float(acc[mt][nt][2]) * rs * cs[nt].z;
+      o[nt][3] = Ops::to_float(acc[mt][nt][3]) * rs * cs[nt].w;
     }
     if (mode == F8_PARTIAL) {
       float* pp = part + (static_cast<int64_t>(s) * M + m) * N + nb0;
@@ -293,18 +325,31 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
   }
 }
 
-// ---------------------------------------------------------------- row quantizer
-__device__ __forceinline__ uint32_t f8_pack4(float a, float b, float c, float d) {
+// ---------------------------------------------------------------- row quantizers
+// Code policies: the largest code magnitude and four scaled, clamped values as one dword of codes.
+struct F8Codes {
+  static constexpr float QMAX = 448.f;
+  static __device__ __forceinline__ uint32_t pack4(float a, float b, float c, float d) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-  return static_cast<uint32_t>(v);
+    int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+    return static_cast<uint32_t>(v);
 #else
-  return 0;
+    return 0;
 #endif
-}
+  }
+};
+struct I8Codes {
+  static constexpr float QMAX = 127.f;
+  // the clamp commutes with the rounding (its ends are integers), so it may come first
+  static __device__ __forceinline__ uint32_t byte(float v) { return static_cast<uint32_t>(static_cast<int>(rintf(v))) & 255u; }
+  static __device__ __forceinline__ uint32_t pack4(float a, float b, float c, float d) {
+    return byte(a) | byte(b) << 8 | byte(c) << 16 | byte(d) << 24;
+  }
+};
 
-__global__ void __launch_bounds__(f8::QT) quant_rows_fp8_kernel(const uint16_t* __restrict__ x, int K,
+template <class Codes>
+__global__ void __launch_bounds__(f8::QT) quant_rows_kernel(const uint16_t* __restrict__ x, int K,
                                                                 uint8_t* __restrict__ codes, float* __restrict__ sx) {
   __shared__ float red[f8::QT / 64];
   const int m = blockIdx.x, tid = threadIdx.x;
@@ -333,7 +378,7 @@ __global__ void __launch_bounds__(f8::QT) quant_rows_fp8_kernel(const uint16_t* 
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < f8::QT / 64; ++i) amax = fmaxf(amax, red[i]);
-  const float sc = fmaxf(amax / 448.f, 1e-12f);
+  const float sc = fmaxf(amax / Codes::QMAX, 1e-12f);
   if (tid == 0) sx[m] = sc;
 #pragma unroll
   for (int i = 0; i < f8::Q_STEPS; ++i) {
@@ -345,9 +390,9 @@ __global__ void __launch_bounds__(f8::QT) quant_rows_fp8_kernel(const uint16_t* 
         float f[8];
         unpack8(v[i][h], f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(f[j] / sc, -448.f), 448.f);
-        o[2 * h] = f8_pack4(f[0], f[1], f[2], f[3]);
-        o[2 * h + 1] = f8_pack4(f[4], f[5], f[6], f[7]);
+        for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(f[j] / sc, -Codes::QMAX), Codes::QMAX);
+        o[2 * h] = Codes::pack4(f[0], f[1], f[2], f[3]);
+        o[2 * h + 1] = Codes::pack4(f[4], f[5], f[6], f[7]);
       }
       st16(cr + 16 * un, make_uint4(o[0], o[1], o[2], o[3]));
     }
@@ -355,15 +400,22 @@ __global__ void __launch_bounds__(f8::QT) quant_rows_fp8_kernel(const uint16_t* 
 }
 
 // x bf16 [M, K] -> codes [M, K], sx [M]. K % 16 == 0, K <= 28,672; 16-B aligned pointers.
-int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st) {
+template <class Codes>
+static int quant_rows(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st) {
   if (x == nullptr || codes == nullptr || sx == nullptr || M < 1 || K < 16 || K % 16 || K > f8::Q_MAX_K) return 1;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(codes)) & 15) return 1;
-  hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3(M), dim3(f8::QT), 0, st, x, K, codes, sx);
+  hipLaunchKernelGGL(quant_rows_kernel<Codes>, dim3(M), dim3(f8::QT), 0, st, x, K, codes, sx);
   return static_cast<int>(hipGetLastError());
 }
+int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st) {
+  return quant_rows<F8Codes>(x, M, K, codes, sx, st);
+}
+int quant_rows_int8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st) {
+  return quant_rows<I8Codes>(x, M, K, codes, sx, st);
+}
 
-// ---------------------------------------------------------------- host side of gemm_f8
-// The launch configurations: (tile rows, LDS ring slots).
+// ---------------------------------------------------------------- host side of gemm_f8 / gemm_i8
+// The launch configurations of both formats: (tile rows, LDS ring slots).
 constexpr F8Cfg F8_CFGS[] = {{256, 2}, {128, 3}};
 constexpr int F8_NCFG = table_size(F8_CFGS);
 int f8_cfgs(const F8Cfg** rows) {
@@ -379,11 +431,17 @@ bool f8_supports(int M, int K, int N, int S, int mode, int cfg) {
   return mode == F8_PARTIAL || ((mode == F8_BF16 || mode == F8_SILU) && S == 1);
 }
 
+// f8_supports, and a whole-K sum of |a w| <= 2^14 that stays inside int32
+constexpr int I8_MAX_K = 131072;
+bool i8_supports(int M, int K, int N, int S, int mode, int cfg) {
+  return K <= I8_MAX_K && f8_supports(M, K, N, S, mode, cfg);
+}
+
 // a codes [M, K], sx [M]; w codes [N, K], sw [N] (16-B aligned); mode F8_PARTIAL: part [S, M, N]
 // fp32; F8_BF16: out [M, N]; F8_SILU: out [M, N / 2]. Returns 0, or 1 for what it cannot take.
-int gemm_f8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
-            uint16_t* out, int S, int mode, int cfg, hipStream_t st) {
-  if (!f8_supports(M, K, N, S, mode, cfg)) return 1;
+template <class Ops>
+static int gemm_8bit(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N,
+                     float* part, uint16_t* out, int S, int mode, int cfg, hipStream_t st) {
   if (a == nullptr || sx == nullptr || w == nullptr || sw == nullptr) return 1;
   if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(sw)) & 15) return 1;
   if (mode == F8_PARTIAL ? part == nullptr : out == nullptr) return 1;
@@ -391,11 +449,21 @@ int gemm_f8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, c
   cfg_dispatch<F8_NCFG>(cfg, [&](auto c) {
     static constexpr F8Cfg f = F8_CFGS[decltype(c)::value];
     const int tiles = ((M + f.bm - 1) / f.bm) * (N / f8::BN);
-    hipLaunchKernelGGL((gemm_f8_kernel<f.bm, f.ns, f.bm <= 128>), dim3(tiles * S), dim3(512), 0, st, a, sx, M, K, w, sw, N, S,
+    hipLaunchKernelGGL((gemm_f8_kernel<Ops, f.bm, f.ns, f.bm <= 128>), dim3(tiles * S), dim3(512), 0, st, a, sx, M, K, w, sw, N, S,
                        part, out, mode);
     rc = static_cast<int>(hipGetLastError());
   });
   return rc;
+}
+int gemm_f8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
+            uint16_t* out, int S, int mode, int cfg, hipStream_t st) {
+  if (!f8_supports(M, K, N, S, mode, cfg)) return 1;
+  return gemm_8bit<F8Ops>(a, sx, M, K, w, sw, N, part, out, S, mode, cfg, st);
+}
+int gemm_i8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
+            uint16_t* out, int S, int mode, int cfg, hipStream_t st) {
+  if (!i8_supports(M, K, N, S, mode, cfg)) return 1;
+  return gemm_8bit<I8Ops>(a, sx, M, K, w, sw, N, part, out, S, mode, cfg, st);
 }
 
 }  // namespace xgk

@@ -477,6 +477,16 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("quant_rows_fp8", [](uintptr_t x, int M, int K, uintptr_t codes, uintptr_t sx, uintptr_t st) {
     check(xgk::quant_rows_fp8(P<const uint16_t>(x), M, K, P<uint8_t>(codes), P<float>(sx), S(st)), "quant_rows_fp8");
   });
+  // the int8 instantiation of the same kernel, and its row quantizer
+  m.def("gemm_i8", [](uintptr_t a, uintptr_t sx, int M, int K, uintptr_t w, uintptr_t sw, int N, uintptr_t part,
+                      uintptr_t out, int splits, int mode, int cfg, uintptr_t st) {
+    check(xgk::gemm_i8(P<const uint8_t>(a), P<const float>(sx), M, K, P<const uint8_t>(w), P<const float>(sw), N,
+                       P<float>(part), P<uint16_t>(out), splits, mode, cfg, S(st)),
+          "gemm_i8");
+  });
+  m.def("quant_rows_int8", [](uintptr_t x, int M, int K, uintptr_t codes, uintptr_t sx, uintptr_t st) {
+    check(xgk::quant_rows_int8(P<const uint16_t>(x), M, K, P<uint8_t>(codes), P<float>(sx), S(st)), "quant_rows_int8");
+  });
   m.def("set_pf_krot", [](int on) { xgk::set_pf_krot(on); });
   m.def("set_k_rotation", [](int mode) { xgk::set_k_rotation(mode); });
   m.def("gemm_m64g_ex", [](uintptr_t x, int M, int K, uintptr_t w, int N, uintptr_t part, uintptr_t out, int splits,
@@ -532,6 +542,7 @@ PYBIND11_MODULE(_kernels, m) {
     py::list lf8;
     for (int i = 0, n = xgk::f8_cfgs(&f8); i < n; ++i) lf8.append(py::make_tuple(f8[i].bm, f8[i].ns));
     d["f8"] = lf8;
+    d["i8"] = lf8;  // gemm_i8 is instantiated from the same table
     return d;
   });
   m.attr("WQ_GROUP") = xgk::WQ_GROUP;
@@ -548,6 +559,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("pf_supports", &xgk::pf_supports);
   m.def("pf_grouped_supports", &xgk::pf_grouped_supports);
   m.def("f8_supports", &xgk::f8_supports);
+  m.def("i8_supports", &xgk::i8_supports);
   m.def("add_partials_resid", [](uintptr_t part, int S_, int T, uintptr_t res, uintptr_t ss_part, int H,
                                  uintptr_t st, uint64_t sim_ticks) {
     if (H % 1024) throw std::invalid_argument("add_partials_resid: H % 1024 != 0");

@@ -37,6 +37,8 @@ def _common(p: argparse.ArgumentParser) -> None:
                    help="with fp8|int8|int4: release the bf16 projection weights and serve from the quantized ones alone")
     p.add_argument("--fp8-activations", action="store_true", default=None,
                    help="with fp8, tp 1: prompt steps above 320 rows quantize activations per token (FP8 matrix instructions)")
+    p.add_argument("--int8-activations", action="store_true", default=None,
+                   help="with int8, tp 1: prompt steps above 320 rows quantize activations per token (INT8 matrix instructions)")
     p.add_argument("--strategy", choices=["round_robin", "least_loaded", "memory_aware"])
     p.add_argument("--batch-mode", choices=["continuous", "static"])
     p.add_argument("--max-num-seqs", type=int)
@@ -55,7 +57,7 @@ def _overrides(a) -> dict:
         "api": {"host": a.host, "port": a.port, "frontends": getattr(a, "frontends", None)},
         "worker": {"model": a.model, "checkpoint": a.checkpoint, "tp": a.tp, "replicas": a.replicas, "gpus": a.gpus,
                    "device": a.device, "quantization": a.quantization, "quantized_only": a.quantized_only,
-                   "fp8_activations": a.fp8_activations,
+                   "fp8_activations": a.fp8_activations, "int8_activations": a.int8_activations,
                    "max_num_seqs": a.max_num_seqs,
                    "max_model_len": a.max_model_len, "mock": a.mock, "in_process": a.in_process,
                    "use_graphs": (False if a.no_graphs else None),

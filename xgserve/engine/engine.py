@@ -130,6 +130,8 @@ class EngineConfig:
     # fp8 models (TP = 1, dense, GPU): prompt steps above 320 rows quantize their activations per
     # token to E4M3 and run on the FP8 matrix instructions (gemm_f8); outputs differ from weight-only
     fp8_activations: bool = False
+    # the same for int8 models: per-token int8 codes on the INT8 matrix instructions (gemm_i8)
+    int8_activations: bool = False
     # custom xGMI all-reduce peer-wait limit while serving: a TP peer this late fails
     # the step (CustomAllReduceTimeout -> replica restart); warmup runs under 20 s
     collective_timeout_s: float = 2.0
@@ -159,7 +161,8 @@ class LLMEngine:
                                                                  checkpoint=cfg.checkpoint, seed=cfg.seed,
                                                                  weight_dtype=cfg.weight_dtype,
                                                                  quantized_only=cfg.quantized_only, mw8=cfg.mw8,
-                                                                 a8=cfg.fp8_activations)
+                                                                 a8=cfg.fp8_activations,
+                                                                 ai8=cfg.int8_activations)
         self.model.set_moe_comm(cfg.moe_comm)
         # static after load: resident weight bytes (parameters + quantized copies) and the
         # quantized-only dequantization scratch, reported by stats()
@@ -937,7 +940,7 @@ class LLMEngine:
             "weight_bytes": self._weight_bytes,
             "scratch_bytes": self._scratch_bytes + (self.spec.scratch_bytes() if self.spec is not None else 0),
             "weight_dtype": getattr(self.model, "weight_dtype", None) or str(self.model.dtype).replace("torch.", ""),
-            "activation_dtype": "fp8" if self.cfg.fp8_activations else "bf16",
+            "activation_dtype": "fp8" if self.cfg.fp8_activations else "int8" if self.cfg.int8_activations else "bf16",
             "cache": cs,
             "preemptions": self.sched.total_preemptions(),
             **self.stats_counters,

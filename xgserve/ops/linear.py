@@ -1008,9 +1008,14 @@ def f8_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
     table (_F8_TUNED is empty): the tile height that pads M least (ties: the taller tile); for
     MODE_PARTIAL the smallest split-K that gives a full round of workgroups (one per CU), capped so
     that every split keeps at least two K tiles; split 1 otherwise."""
+    return _f8_rule(M, N, K, mode, cus, _F8_TUNED, _f8_valid)
+
+
+def _f8_rule(M: int, N: int, K: int, mode: int, cus: int, tuned: dict, valid):
+    """f8_plan's rule, shared with i8_plan (same tiles; `tuned` and `valid` are the format's)."""
     if M < 1 or K % F8_KT or N % F8_COLS or K > F8_QUANT_MAX_K:
         return None
-    t = _F8_TUNED.get((N, K, mode), {}).get(M)
+    t = tuned.get((N, K, mode), {}).get(M)
     if t is None:
         cfg = min(F8_CFGS, key=lambda c: (-(-M // F8_CFGS[c][0]) * F8_CFGS[c][0], -F8_CFGS[c][0]))
         S = 1
@@ -1018,7 +1023,7 @@ def f8_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
             tiles = -(-M // F8_CFGS[cfg][0]) * (N // F8_COLS)
             S = max(1, min(-(-cus // tiles), K // (2 * F8_KT)))
         t = (S, cfg)
-    return t if _f8_valid(M, N, K, mode, t[0], t[1]) else None
+    return t if valid(M, N, K, mode, t[0], t[1]) else None
 
 
 def f8_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MODE_PARTIAL,
@@ -1026,8 +1031,13 @@ def f8_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, sw: torc
     """gemm_f8 on codes given: a [M, K] / q [N, K] uint8 E4M3, sx [M] / sw [N] fp32. Returns what
     pf_linear returns for the dequantized operands: bf16 [M, N] (MODE_BF16), a PendingSum
     (MODE_PARTIAL) or silu(gate) * up [M, N / 2] of a block-16 interleaved gate|up weight."""
+    return _codes_linear("gemm_f8", f8_plan, _f8_valid, a, sx, q, sw, mode, plan, out)
+
+
+def _codes_linear(name: str, plan_of, valid, a, sx, q, sw, mode, plan, out):
+    """The checks and the launch of f8_linear_codes / i8_linear_codes (`name`: the native entry)."""
     def bad(what):
-        return ValueError(f"gemm_f8: {what}")
+        return ValueError(f"{name}: {what}")
 
     if a.dim() != 2 or q.dim() != 2 or a.dtype != torch.uint8 or q.dtype != torch.uint8:
         raise bad(f"a and q must be 2-d uint8 codes, got {a.dtype} {tuple(a.shape)} and {q.dtype} {tuple(q.shape)}")
@@ -1047,13 +1057,13 @@ def f8_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, sw: torc
         if (mode == MODE_PARTIAL or out.dtype != torch.bfloat16 or out.device != a.device
                 or not out.is_contiguous() or tuple(out.shape) != shape):
             raise bad(f"out must be a contiguous bfloat16 {shape} on {a.device} (bf16 / SiLU modes only)")
-    p = plan or f8_plan(M, N, K, mode, cu_count(a.device))
-    if p is None or len(p) != 2 or not _f8_valid(M, N, K, mode, p[0], p[1]):
+    p = plan or plan_of(M, N, K, mode, cu_count(a.device))
+    if p is None or len(p) != 2 or not valid(M, N, K, mode, p[0], p[1]):
         raise bad(f"unsupported M={M} N={N} K={K} mode={mode} plan={p}")
     S, cfg = p
     res, part, outp = _result(a, M, N, S, mode, out)
-    kernels().gemm_f8(a.data_ptr(), sx.data_ptr(), M, K, q.data_ptr(), sw.data_ptr(), N, part, outp, S, mode, cfg,
-                      stream_ptr())
+    getattr(kernels(), name)(a.data_ptr(), sx.data_ptr(), M, K, q.data_ptr(), sw.data_ptr(), N, part, outp, S, mode, cfg,
+                             stream_ptr())
     return res
 
 
@@ -1067,3 +1077,69 @@ def f8_linear(x: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MO
         raise ValueError(f"gemm_f8: unsupported M={x.shape[0]} N={q.shape[0]} K={x.shape[1]} mode={mode}")
     a, sx = quant_rows_fp8(x)
     return f8_linear_codes(a, sx, q, sw, mode, plan, out)
+
+
+# ---------------------------------------------------------------------------- gemm_i8 (int8 codes x int8 codes, M > 320)
+# The int8 instantiation of the gemm_f8 kernel (csrc/kernels/gemm_f8.hip, I8Ops): prompt-sized steps of
+# an int8 model on v_mfma_i32_16x16x64_i8. The activations are quantized per row (token) to int8
+# with a dynamic scale, the weight codes are read as quantize_int8 stores them, the products are
+# summed in int32 and both scales are applied to the converted sum:
+#   out = diag(sx) (A . W^T) diag(sw)
+# Tiles, cfgs (F8_CFGS) and the plan rule are gemm_f8's; the only difference in what it takes is K.
+I8_MAX_K = 131072  # a whole-K sum of |a w| <= 2^14 stays inside int32
+_I8_TUNED = {}     # (N, K, mode) -> {M: (split_k, cfg)}: empty until somebody sweeps it
+
+
+def quantize_rows_int8(x: torch.Tensor):
+    """[M, K] -> (int8 codes as uint8 [M, K], fp32 per-row scales [M]): quantize_int8 by rows, i.e.
+    one dynamic scale per token, sx = max(max|x_row| / 127, 1e-12), code = round-half-even(x / sx)
+    in -127 .. 127. The definition that the HIP quantizer (quant_rows_int8) reproduces bit for bit,
+    and the CPU path."""
+    return quantize_int8(x)
+
+
+def quant_rows_int8(x: torch.Tensor):
+    """quantize_rows_int8 of a bf16 [M, K] on its device: the HIP kernel on a GPU, PyTorch elsewhere."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError(f"quant_rows_int8: x must be a contiguous 2-d bfloat16, got {x.dtype} {tuple(x.shape)}")
+    M, K = x.shape
+    if not use_native(x):
+        return quantize_rows_int8(x)
+    if M < 1 or K < 16 or K % 16 or K > F8_QUANT_MAX_K:
+        raise ValueError(f"quant_rows_int8: needs M >= 1, K % 16 == 0, 16 <= K <= {F8_QUANT_MAX_K}, got M={M} K={K}")
+    codes = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    sx = torch.empty(M, dtype=torch.float32, device=x.device)
+    kernels().quant_rows_int8(x.data_ptr(), M, K, codes.data_ptr(), sx.data_ptr(), stream_ptr())
+    return codes, sx
+
+
+def _i8_valid(M: int, N: int, K: int, mode: int, S: int, cfg: int) -> bool:
+    """gemm_f8.hip i8_supports: f8_supports and a K whose sums stay inside int32."""
+    return K <= I8_MAX_K and _f8_valid(M, N, K, mode, S, cfg)
+
+
+@functools.lru_cache(maxsize=4096)
+def i8_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
+    """(split_k, cfg) for gemm_i8, or None when the shape is unsupported: f8_plan's rule (same
+    tiles, same K tile, same row quantizer limit) over a table of its own, _I8_TUNED."""
+    return _f8_rule(M, N, K, mode, cus, _I8_TUNED, _i8_valid)
+
+
+def i8_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MODE_PARTIAL,
+                    plan=None, out: Optional[torch.Tensor] = None):
+    """gemm_i8 on codes given: a [M, K] / q [N, K] int8 codes as uint8, sx [M] / sw [N] fp32. Returns
+    what f8_linear_codes returns: bf16 [M, N] (MODE_BF16), a PendingSum (MODE_PARTIAL) or
+    silu(gate) * up [M, N / 2] of a block-16 interleaved gate|up weight."""
+    return _codes_linear("gemm_i8", i8_plan, _i8_valid, a, sx, q, sw, mode, plan, out)
+
+
+def i8_linear(x: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MODE_PARTIAL, plan=None,
+              out: Optional[torch.Tensor] = None):
+    """x bf16 [M, K] quantized per row to int8 (quant_rows_int8), then gemm_i8 against the int8
+    weight (q, sw) of quantize_int8: W8A8 with dynamic per-token scales."""
+    if x.dim() != 2 or q.dim() != 2 or x.shape[1] != q.shape[1] or not x.is_cuda or x.device != q.device:
+        raise ValueError(f"gemm_i8: x {tuple(x.shape)} on {x.device} does not go with q {tuple(q.shape)} on {q.device}")
+    if plan is None and i8_plan(x.shape[0], q.shape[0], x.shape[1], mode, cu_count(x.device)) is None:
+        raise ValueError(f"gemm_i8: unsupported M={x.shape[0]} N={q.shape[0]} K={x.shape[1]} mode={mode}")
+    a, sx = quant_rows_int8(x)
+    return i8_linear_codes(a, sx, q, sw, mode, plan, out)

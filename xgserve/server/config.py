@@ -112,6 +112,8 @@ class WorkerSection:
     # their activations per token to E4M3 and run on the FP8 matrix instructions (gemm_f8), so
     # outputs differ from the weight-only server's; smaller steps stay weight-only
     fp8_activations: bool = False
+    # the same with quantization int8: per-token int8 codes on the INT8 matrix instructions (gemm_i8)
+    int8_activations: bool = False
     block_size: int = 16
     max_num_seqs: int = 256
     max_num_batched_tokens: int = 8192
@@ -223,18 +225,22 @@ class ServerConfig:
             e.append(f"worker.quantized_only needs worker.quantization fp8|int8|int4, got {w.quantization!r}")
         if w.quantized_only and w.device == "cpu":
             e.append("worker.quantized_only needs a GPU (worker.device is cpu)")
-        if w.fp8_activations:
-            if w.quantization != "fp8":
-                e.append(f"worker.fp8_activations needs worker.quantization fp8, got {w.quantization!r}")
+        if w.fp8_activations and w.int8_activations:
+            e.append("worker.fp8_activations and worker.int8_activations exclude each other (one weight format)")
+        for key, need in (("fp8_activations", "fp8"), ("int8_activations", "int8")):
+            if not getattr(w, key):
+                continue
+            if w.quantization != need:
+                e.append(f"worker.{key} needs worker.quantization {need}, got {w.quantization!r}")
             if w.device == "cpu":
-                e.append("worker.fp8_activations needs a GPU (worker.device is cpu)")
+                e.append(f"worker.{key} needs a GPU (worker.device is cpu)")
             if w.tp != 1:
-                e.append(f"worker.fp8_activations needs worker.tp = 1, got {w.tp}")
+                e.append(f"worker.{key} needs worker.tp = 1, got {w.tp}")
             if not w.mock:
                 try:
                     from ..models.config import get_config
                     if get_config(w.checkpoint or w.model).arch == "mixtral":
-                        e.append("worker.fp8_activations does not cover Mixtral (dense Llama models only)")
+                        e.append(f"worker.{key} does not cover Mixtral (dense Llama models only)")
                 except Exception:  # (an unknown model is reported below)
                     pass
         if not (0.0 < w.gpu_memory_utilization <= 1.0):
