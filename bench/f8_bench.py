@@ -9,7 +9,9 @@ gemm_bench.graph_us, the three candidates alternating within one call:
 One JSON line per (shape, M, op): us and achieved TFLOP/s from 2 M N K.
 --format int8: the same table for gemm_i8 (int8 weights, per-token int8 activations, INT8 matrix
 instructions) beside dequantize + library of the int8 weight and the same bf16 gemm_pf.
-  python bench/f8_bench.py [--format fp8|int8] [--shapes qkv o gate_up down ...] [--M 384 576 1024 2048 8192]"""
+--format int4: the same for gemm_i4 (packed int4 weights with 128-k group scales, per-token int8
+activations in the kernel's k order).
+  python bench/f8_bench.py [--format fp8|int8|int4] [--shapes qkv o gate_up down ...] [--M 384 576 1024 2048 8192]"""
 import argparse
 import json
 import os
@@ -30,12 +32,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["qkv", "o", "gate_up", "down", "qkv70", "o70", "gate_up70", "down70"])
     ap.add_argument("--M", type=int, nargs="+", default=[384, 576, 1024, 2048, 8192])
-    ap.add_argument("--format", choices=["fp8", "int8"], default="fp8")
+    ap.add_argument("--format", choices=["fp8", "int8", "int4"], default="fp8")
     a = ap.parse_args()
     kernels()
     fam, fmt, quantize, dequantize, plan_of, linear, quant_rows = {
         "fp8": ("f8", L.WQ_FP8, L.quantize_fp8, L.dequantize_fp8, L.f8_plan, L.f8_linear, L.quant_rows_fp8),
-        "int8": ("i8", L.WQ_INT8, L.quantize_int8, L.dequantize_int8, L.i8_plan, L.i8_linear, L.quant_rows_int8)}[a.format]
+        "int8": ("i8", L.WQ_INT8, L.quantize_int8, L.dequantize_int8, L.i8_plan, L.i8_linear, L.quant_rows_int8),
+        "int4": ("i4", L.WQ_INT4, L.quantize_int4, L.dequantize_int4, L.i4_plan, L.i4_linear, L.quant_rows_int8_i4)}[a.format]
     for name in a.shapes:
         N, K = SHAPES[name]
         mode = L.MODE_SILU if name.startswith("gate_up") else L.MODE_PARTIAL

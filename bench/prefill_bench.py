@@ -107,9 +107,9 @@ def main():
     ap.add_argument("--fp8-activations-pair", action="store_true",
                     help="with --quantization fp8: the TTFT without and then with fp8 activations, in this one call")
     ap.add_argument("--int8-activations", action="store_true",
-                    help="with --quantization int8: prompt steps above 320 rows on gemm_i8 (activations quantized per token)")
+                    help="with --quantization int8 / int4: prompt steps above 320 rows on gemm_i8 / gemm_i4 (activations quantized per token)")
     ap.add_argument("--int8-activations-pair", action="store_true",
-                    help="with --quantization int8: the TTFT without and then with int8 activations, in this one call")
+                    help="with --quantization int8 / int4: the TTFT without and then with int8 activations, in this one call")
     a = ap.parse_args()
     kernels()
     for name, Hq, Hkv in (("llama3-8b", 32, 8), ("llama3-70b", 64, 8)):

@@ -1,5 +1,5 @@
 // Host side of the hand-written GEMM families (gemm_m64g.hip dense and grouped,
-// gemm_w8.hip, moe_gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped, gemm_f8.hip): the one declaration of their
+// gemm_w8.hip, moe_gemm_w8.hip, gemm_mw.hip, gemm_mw8.hip, gemm_pf.hip dense and grouped, gemm_f8.hip, gemm_i4.hip): the one declaration of their
 // entry points, of the row type of each family's configuration table (the table itself
 // sits next to its kernel) and of the no-launch shape predicates, shared by the kernels'
 // translation units and the pybind11 layer (ops.cpp).
@@ -42,6 +42,9 @@ struct PfCfg {
 struct F8Cfg {
   int bm, ns;  // tile rows, LDS ring slots (one 128-deep K tile of codes each)
 };
+struct I4Cfg {
+  int bm, ns;  // tile rows, LDS ring slots (one 128-deep K tile of A codes, packed W codes and group scales each)
+};
 int m64g_cfgs(const M64Cfg** rows);
 int w8_cfgs(const W8Cfg** rows);
 int moe_w8_cfgs(const W8Cfg** rows);
@@ -49,6 +52,7 @@ int mw_cfgs(const MwCfg** rows);
 int mw8_cfgs(const Mw8Cfg** rows);
 int pf_cfgs(const PfCfg** rows);
 int f8_cfgs(const F8Cfg** rows);
+int i4_cfgs(const I4Cfg** rows);
 
 constexpr int M64G_MAX_M = 64, W8_MAX_M = 64, MW_MAX_M = 320;
 constexpr int WQ_GROUP = 128;       // k per int4 scale group
@@ -65,6 +69,7 @@ bool pf_supports(int M, int K, int N, int S, int mode, int cfg);
 bool pf_grouped_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg);
 bool f8_supports(int M, int K, int N, int S, int mode, int cfg);
 bool i8_supports(int M, int K, int N, int S, int mode, int cfg);  // f8_supports and K <= 131,072
+bool i4_supports(int M, int K, int N, int S, int mode, int cfg);
 
 // GG_MOE_RESID (grouped w2 of the fused decode layer, TP = 1): the MoE combine inside
 // the w2 launch. Every workgroup stores its fp32 partial rows write-through and takes a
@@ -126,5 +131,12 @@ int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, h
 int gemm_i8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
             uint16_t* out, int S, int mode, int cfg, hipStream_t st);
 int quant_rows_int8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
+// gemm_i4.hip: int8 row codes against the packed int4 codes of quantize_int4 (w [N, K / 2], group scales
+// gs [K / 128, N]) on v_mfma_i32_16x16x64_i8, one int32 sum per 128-k group folded into fp32 with the
+// group's scale. a is in kernel order: within every 16 k the bytes are k (0, 4, 1, 5), (8, 12, 9, 13),
+// (2, 6, 3, 7), (10, 14, 11, 15); quant_rows_int8_i4 is quant_rows_int8 storing that order
+int gemm_i4(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* gs, int N, float* part,
+            uint16_t* out, int S, int mode, int cfg, hipStream_t st);
+int quant_rows_int8_i4(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
 
 }  // namespace xgk

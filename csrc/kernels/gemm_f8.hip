@@ -14,6 +14,8 @@
 // a split converts its own sum, so a slab is float(sum_s) * sx * sw. quant_rows_int8 is
 // quant_rows_fp8 with sx = max(amax / 127, 1e-12) and code = clamp(rint(x / sx), -127, 127)
 // (v_rndne_f32: round half to even), bit-identical to quantize_rows_int8 of xgserve/ops/linear.py.
+// quant_rows_int8_i4 is quant_rows_int8 storing every 16 consecutive k in the byte order that
+// gemm_i4.hip multiplies without a shuffle (I8CodesI4::K_OF, i4_order of xgserve/ops/linear.py).
 // What follows describes gemm_f8; read "K = 128 instruction" as the instruction pair for int8.
 //
 // A and W are OCP E4M3 codes (W as quantize_fp8 stores it: [N, K] row-major, one fp32 scale per
@@ -326,8 +328,12 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
 }
 
 // ---------------------------------------------------------------- row quantizers
-// Code policies: the largest code magnitude and four scaled, clamped values as one dword of codes.
-struct F8Codes {
+// Code policies: the largest code magnitude, four scaled, clamped values as one dword of codes, and
+// K_OF[b]: which of 16 consecutive k is stored as byte b of their 16 B.
+struct NaturalOrder {
+  static constexpr int K_OF[16] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};
+};
+struct F8Codes : NaturalOrder {
   static constexpr float QMAX = 448.f;
   static __device__ __forceinline__ uint32_t pack4(float a, float b, float c, float d) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -339,13 +345,19 @@ struct F8Codes {
 #endif
   }
 };
-struct I8Codes {
+struct I8Arith {
   static constexpr float QMAX = 127.f;
   // the clamp commutes with the rounding (its ends are integers), so it may come first
   static __device__ __forceinline__ uint32_t byte(float v) { return static_cast<uint32_t>(static_cast<int>(rintf(v))) & 255u; }
   static __device__ __forceinline__ uint32_t pack4(float a, float b, float c, float d) {
     return byte(a) | byte(b) << 8 | byte(c) << 16 | byte(d) << 24;
   }
+};
+struct I8Codes : I8Arith, NaturalOrder {};
+// the kernel order of gemm_i4.hip (i4_order of xgserve/ops/linear.py): the k that the "even" and the
+// "odd" widened words of a packed int4 weight hold, so that gemm_i4 selects registers, not bytes
+struct I8CodesI4 : I8Arith {
+  static constexpr int K_OF[16] = {0, 4, 1, 5, 8, 12, 9, 13, 2, 6, 3, 7, 10, 14, 11, 15};
 };
 
 template <class Codes>
@@ -385,15 +397,16 @@ __global__ void __launch_bounds__(f8::QT) quant_rows_kernel(const uint16_t* __re
     const int un = tid + i * f8::QT;
     if (un < units) {
       uint32_t o[4];
+      float f[16];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        float f[8];
-        unpack8(v[i][h], f);
+        unpack8(v[i][h], f + 8 * h);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(f[j] / sc, -Codes::QMAX), Codes::QMAX);
-        o[2 * h] = Codes::pack4(f[0], f[1], f[2], f[3]);
-        o[2 * h + 1] = Codes::pack4(f[4], f[5], f[6], f[7]);
+        for (int j = 0; j < 8; ++j) f[8 * h + j] = fminf(fmaxf(f[8 * h + j] / sc, -Codes::QMAX), Codes::QMAX);
       }
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        o[d] = Codes::pack4(f[Codes::K_OF[4 * d]], f[Codes::K_OF[4 * d + 1]], f[Codes::K_OF[4 * d + 2]], f[Codes::K_OF[4 * d + 3]]);
       st16(cr + 16 * un, make_uint4(o[0], o[1], o[2], o[3]));
     }
   }
@@ -412,6 +425,9 @@ int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, h
 }
 int quant_rows_int8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st) {
   return quant_rows<I8Codes>(x, M, K, codes, sx, st);
+}
+int quant_rows_int8_i4(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st) {
+  return quant_rows<I8CodesI4>(x, M, K, codes, sx, st);
 }
 
 // ---------------------------------------------------------------- host side of gemm_f8 / gemm_i8

@@ -487,6 +487,17 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("quant_rows_int8", [](uintptr_t x, int M, int K, uintptr_t codes, uintptr_t sx, uintptr_t st) {
     check(xgk::quant_rows_int8(P<const uint16_t>(x), M, K, P<uint8_t>(codes), P<float>(sx), S(st)), "quant_rows_int8");
   });
+  // gemm_i4.hip: int8 row codes in kernel order against packed int4 codes and their group scales
+  m.def("gemm_i4", [](uintptr_t a, uintptr_t sx, int M, int K, uintptr_t w, uintptr_t gs, int N, uintptr_t part,
+                      uintptr_t out, int splits, int mode, int cfg, uintptr_t st) {
+    check(xgk::gemm_i4(P<const uint8_t>(a), P<const float>(sx), M, K, P<const uint8_t>(w), P<const float>(gs), N,
+                       P<float>(part), P<uint16_t>(out), splits, mode, cfg, S(st)),
+          "gemm_i4");
+  });
+  m.def("quant_rows_int8_i4", [](uintptr_t x, int M, int K, uintptr_t codes, uintptr_t sx, uintptr_t st) {
+    check(xgk::quant_rows_int8_i4(P<const uint16_t>(x), M, K, P<uint8_t>(codes), P<float>(sx), S(st)),
+          "quant_rows_int8_i4");
+  });
   m.def("set_pf_krot", [](int on) { xgk::set_pf_krot(on); });
   m.def("set_k_rotation", [](int mode) { xgk::set_k_rotation(mode); });
   m.def("gemm_m64g_ex", [](uintptr_t x, int M, int K, uintptr_t w, int N, uintptr_t part, uintptr_t out, int splits,
@@ -543,6 +554,10 @@ PYBIND11_MODULE(_kernels, m) {
     for (int i = 0, n = xgk::f8_cfgs(&f8); i < n; ++i) lf8.append(py::make_tuple(f8[i].bm, f8[i].ns));
     d["f8"] = lf8;
     d["i8"] = lf8;  // gemm_i8 is instantiated from the same table
+    const xgk::I4Cfg* i4;
+    py::list li4;
+    for (int i = 0, n = xgk::i4_cfgs(&i4); i < n; ++i) li4.append(py::make_tuple(i4[i].bm, i4[i].ns));
+    d["i4"] = li4;
     return d;
   });
   m.attr("WQ_GROUP") = xgk::WQ_GROUP;
@@ -560,6 +575,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("pf_grouped_supports", &xgk::pf_grouped_supports);
   m.def("f8_supports", &xgk::f8_supports);
   m.def("i8_supports", &xgk::i8_supports);
+  m.def("i4_supports", &xgk::i4_supports);
   m.def("add_partials_resid", [](uintptr_t part, int S_, int T, uintptr_t res, uintptr_t ss_part, int H,
                                  uintptr_t st, uint64_t sim_ticks) {
     if (H % 1024) throw std::invalid_argument("add_partials_resid: H % 1024 != 0");

@@ -38,7 +38,7 @@ def _common(p: argparse.ArgumentParser) -> None:
     p.add_argument("--fp8-activations", action="store_true", default=None,
                    help="with fp8, tp 1: prompt steps above 320 rows quantize activations per token (FP8 matrix instructions)")
     p.add_argument("--int8-activations", action="store_true", default=None,
-                   help="with int8, tp 1: prompt steps above 320 rows quantize activations per token (INT8 matrix instructions)")
+                   help="with int8 or int4, tp 1: prompt steps above 320 rows quantize activations per token (INT8 matrix instructions)")
     p.add_argument("--strategy", choices=["round_robin", "least_loaded", "memory_aware"])
     p.add_argument("--batch-mode", choices=["continuous", "static"])
     p.add_argument("--max-num-seqs", type=int)

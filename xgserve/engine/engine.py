@@ -130,7 +130,8 @@ class EngineConfig:
     # fp8 models (TP = 1, dense, GPU): prompt steps above 320 rows quantize their activations per
     # token to E4M3 and run on the FP8 matrix instructions (gemm_f8); outputs differ from weight-only
     fp8_activations: bool = False
-    # the same for int8 models: per-token int8 codes on the INT8 matrix instructions (gemm_i8)
+    # the same for int8 and int4 models: per-token int8 codes on the INT8 matrix instructions
+    # (gemm_i8; int4 weights: gemm_i4)
     int8_activations: bool = False
     # custom xGMI all-reduce peer-wait limit while serving: a TP peer this late fails
     # the step (CustomAllReduceTimeout -> replica restart); warmup runs under 20 s

@@ -51,7 +51,7 @@ from ..ops import linear as linear_mod
 from ..ops.linear import (MODE_BF16, MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M, W8_MIN_ELEMS, PendingSum,
                           ResidWorkspace, RowStats, dequantize_into, lm_head_linear, m64_ar_resid_linear,
                           m64_linear, m64_plan, m64_resid_linear,
-                          f8_linear, f8_plan, i8_linear, i8_plan, mw8_linear, mw8_plan, mw_linear, mw_plan, pf_linear, pf_plan,
+                          f8_linear, f8_plan, i4_linear, i4_plan, i8_linear, i8_plan, mw8_linear, mw8_plan, mw_linear, mw_plan, pf_linear, pf_plan,
                           quantize_expert_stack, quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
                           w8_plan, WQ_FORMATS)
 from ..ops.moe import moe_w8_plan
@@ -155,7 +155,7 @@ PROJECTIONS = ("qkv", "o", "gate_up", "down")
 
 class Step(NamedTuple):
     """The GEMM kernel family of each projection at one step -- "w8", "skinny", "m64",
-    "mw", "mw8", "pf", "f8", "i8" (HIP: QKV / O / down as split-K partials into their consumers, the SiLU
+    "mw", "mw8", "pf", "f8", "i8", "i4" (HIP: QKV / O / down as split-K partials into their consumers, the SiLU
     gate inside gate_up), "lib" (library GEMM, bf16 out) or "dq" (the quantized weight
     dequantized into the model's scratch, then the library GEMM) -- and the attention entry:
     "fused_decode" / "from_partials" for QKV partials, "rope" for a QKV tensor. MoE
@@ -200,6 +200,7 @@ class LayerDispatch:
         self.mw8: Optional[Step] = None          # W8_MAX_M < T <= MW_MAX_TOKENS with a projection on gemm_mw8
         self.f8: tuple = ()                      # projections that run T > MW_MAX_TOKENS on gemm_f8 (a8)
         self.i8: tuple = ()                      # ... on gemm_i8 (ai8)
+        self.i4: tuple = ()                      # ... on gemm_i4 (aw4: int8 activations on int4 copies)
         self.on_gpu, self.tp = on_gpu, tp
         self.fast_ok = on_gpu and H % 256 == 0 and HqD % 256 == 0 and Nqkv % 64 == 0 and (moe or Fl % 256 == 0)
         shapes = ((Nqkv, H, MODE_PARTIAL), (H, HqD, MODE_PARTIAL))
@@ -227,7 +228,8 @@ class LayerDispatch:
                    on_gpu, attn_fq_ok)
 
     def set_quantized(self, names, resident: bool = True, fmt: Optional[int] = None, a8: bool = False,
-                      a8_fmt: Optional[int] = None, ai8: bool = False, ai8_fmt: Optional[int] = None) -> None:
+                      a8_fmt: Optional[int] = None, ai8: bool = False, ai8_fmt: Optional[int] = None,
+                      aw4: bool = False, aw4_fmt: Optional[int] = None) -> None:
         """The projections in `names` have fp8 / int8 / int4 copies (gemm_w8, T <= W8_MAX_M);
         the others run their bf16 weight on gemm_m64g there. resident=False: the bf16
         weights of `names` are gone, so every larger step dequantizes them into the
@@ -243,10 +245,17 @@ class LayerDispatch:
         ("f8": rows quantized to E4M3 per token, then the FP8 matrix instructions on the codes);
         the others keep that step's family of today. Otherwise a8 changes nothing.
         ai8 / ai8_fmt (int8 activations): the same for int8 copies, i8_plan and gemm_i8 ("i8": rows
-        quantized to int8 per token, then the INT8 matrix instructions). a8 stays fp8 only."""
+        quantized to int8 per token, then the INT8 matrix instructions). a8 stays fp8 only.
+        aw4 / aw4_fmt (int8 activations on int4 weights): the same for int4 copies, i4_plan and
+        gemm_i4 ("i4": rows quantized to int8 per token in the kernel's k order, then the INT8 matrix
+        instructions on the widened int4 codes, one group scale per K tile). ai8 stays int8 only."""
         a8_fmt = fmt if a8_fmt is None else a8_fmt
         ai8_fmt = fmt if ai8_fmt is None else ai8_fmt
-        self.f8 = self.i8 = ()
+        aw4_fmt = fmt if aw4_fmt is None else aw4_fmt
+        self.f8 = self.i8 = self.i4 = ()
+        if aw4 and aw4_fmt == linear_mod.WQ_INT4 and self.on_gpu and self.tp == 1 and "gate_up" in self.shapes:
+            self.i4 = tuple(n for n in PROJECTIONS if n in names
+                            and i4_plan(MW_MAX_TOKENS + 1, *self.shapes[n]) is not None)
         if ai8 and ai8_fmt == linear_mod.WQ_INT8 and self.on_gpu and self.tp == 1 and "gate_up" in self.shapes:
             self.i8 = tuple(n for n in PROJECTIONS if n in names
                             and i8_plan(MW_MAX_TOKENS + 1, *self.shapes[n]) is not None)
@@ -271,13 +280,15 @@ class LayerDispatch:
 
     def select(self, T: int, num_decodes: int, mixed_graph: bool = False) -> Step:
         """mixed_graph: a body of the runner's mixed-step graphs (AttnMeta.mixed_graph), which keep
-        the families they had: no "mw8", no "f8" / "i8". Decode graphs and eager steps take them."""
+        the families they had: no "mw8", no "f8" / "i8" / "i4". Decode graphs and eager steps take them."""
         today = self._select(T, num_decodes, mixed_graph)
-        a8, on8 = ("f8", self.f8) if self.f8 else ("i8", self.i8)  # (the copies have one format)
-        if not on8 or T <= MW_MAX_TOKENS or mixed_graph:
+        if T <= MW_MAX_TOKENS or mixed_graph:
             return today
-        fam = [a8 if n in on8 else getattr(today, n) for n in PROJECTIONS]
-        return Step(*fam, "from_partials" if fam[0] in (a8, "pf") else "rope")
+        for a8, on8 in (("f8", self.f8), ("i8", self.i8), ("i4", self.i4)):  # (the copies have one format)
+            if on8:
+                fam = [a8 if n in on8 else getattr(today, n) for n in PROJECTIONS]
+                return Step(*fam, "from_partials" if fam[0] in (a8, "pf") else "rope")
+        return today
 
     def _select(self, T: int, num_decodes: int, mixed_graph: bool) -> Step:
         if self.quantized is not None and T <= W8_MAX_M:
@@ -372,6 +383,9 @@ class LlamaLayer(nn.Module):
         if family == "i8":
             q = self.w8[name]
             return i8_linear(x, q[0], q[1], mode)
+        if family == "i4":
+            q = self.w8[name]
+            return i4_linear(x, q[0], q[1], mode)
         if family == "dq":
             # One scratch for every projection of every layer: the whole step runs on one
             # stream, so the GEMM that reads the scratch is enqueued before the next
@@ -724,16 +738,17 @@ class LlamaForCausalLM(nn.Module):
         (gemm_f8), for resident and quantized-only models alike. Outputs then differ from the
         weight-only model's. Smaller steps stay weight-only.
         ai8 (EngineConfig.int8_activations): the same for int8 models -- per-token int8 codes,
-        i8_plan, the INT8 matrix instructions (gemm_i8)."""
+        i8_plan, the INT8 matrix instructions (gemm_i8) -- and for int4 models: the same codes
+        against the packed int4 weights, i4_plan, gemm_i4 (one int32 sum per 128-k scale group)."""
         fmt = WQ_FORMATS[kind]
         l0 = self.layers[0]
         moe = any(l.moe for l in self.layers)
-        for on, key, need in ((a8, "a8", "fp8"), (ai8, "ai8", "int8")):
+        for on, key, need in ((a8, "a8", ("fp8",)), (ai8, "ai8", ("int8", "int4"))):
             if on:
-                why = [t for c, t in ((kind != need, f"{need} weights, not {kind}"), (self.tp != 1, "TP = 1"),
+                why = [t for c, t in ((kind not in need, f"{' or '.join(need)} weights, not {kind}"), (self.tp != 1, "TP = 1"),
                                       (moe, "a dense model, not Mixtral"), (self.device.type != "cuda", "a GPU")) if c]
                 if why:
-                    raise ValueError(f"{need} activations ({key}) need " + ", ".join(why))
+                    raise ValueError(f"{need[0]} activations ({key}) need " + ", ".join(why))
         if self.device.type != "cuda" or (moe and (self.tp != 1 or quantized_only)):
             return False
         if moe:  # the experts at both ends of every row body and at the largest quantized step
@@ -758,7 +773,7 @@ class LlamaForCausalLM(nn.Module):
             if l.moe:  # expert copies beside the resident bf16 experts (which larger steps read)
                 l.w8.update({n: quantize_expert_stack(getattr(l, n), fmt) + (fmt,) for n in ("w13", "w2")})
             l.dispatch.set_quantized(chosen, resident=not quantized_only, fmt=fmt if mw8 else None, a8=a8, a8_fmt=fmt,
-                                     ai8=ai8, ai8_fmt=fmt)
+                                     ai8=ai8, ai8_fmt=fmt, aw4=ai8, aw4_fmt=fmt)
             if quantized_only:
                 for n in chosen:
                     l.released[n] = tuple(getattr(l, n).shape)

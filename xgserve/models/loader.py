@@ -38,9 +38,10 @@ def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = N
     mw8: 65..320-row steps of the quantized model read the codes on gemm_mw8
     (LlamaForCausalLM.quantize_weights). a8: fp8 activations on prompt steps above 320 rows
     (gemm_f8; fp8 weights, TP = 1, dense models on a GPU -- anything else raises). ai8: int8
-    activations on the same steps of an int8 model (gemm_i8; the same conditions)."""
-    if ai8 and weight_dtype != "int8":
-        raise ValueError(f"int8 activations (ai8) need weight_dtype int8, got {weight_dtype!r}")
+    activations on the same steps of an int8 model (gemm_i8; the same conditions) or of an int4 model
+    (gemm_i4)."""
+    if ai8 and weight_dtype not in ("int8", "int4"):
+        raise ValueError(f"int8 activations (ai8) need weight_dtype int8 or int4, got {weight_dtype!r}")
     if a8 and weight_dtype != "fp8":
         raise ValueError(f"fp8 activations (a8) need weight_dtype fp8, got {weight_dtype!r}")
     if quantized_only and weight_dtype not in ("fp8", "int8", "int4"):

@@ -1011,16 +1011,18 @@ def f8_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
     return _f8_rule(M, N, K, mode, cus, _F8_TUNED, _f8_valid)
 
 
-def _f8_rule(M: int, N: int, K: int, mode: int, cus: int, tuned: dict, valid):
-    """f8_plan's rule, shared with i8_plan (same tiles; `tuned` and `valid` are the format's)."""
+def _f8_rule(M: int, N: int, K: int, mode: int, cus: int, tuned: dict, valid, cfgs=None):
+    """f8_plan's rule, shared with i8_plan and i4_plan (`tuned`, `valid` and the cfg table `cfgs`
+    are the format's; the table defaults to F8_CFGS)."""
+    cfgs = F8_CFGS if cfgs is None else cfgs
     if M < 1 or K % F8_KT or N % F8_COLS or K > F8_QUANT_MAX_K:
         return None
     t = tuned.get((N, K, mode), {}).get(M)
     if t is None:
-        cfg = min(F8_CFGS, key=lambda c: (-(-M // F8_CFGS[c][0]) * F8_CFGS[c][0], -F8_CFGS[c][0]))
+        cfg = min(cfgs, key=lambda c: (-(-M // cfgs[c][0]) * cfgs[c][0], -cfgs[c][0]))
         S = 1
         if mode == MODE_PARTIAL:
-            tiles = -(-M // F8_CFGS[cfg][0]) * (N // F8_COLS)
+            tiles = -(-M // cfgs[cfg][0]) * (N // F8_COLS)
             S = max(1, min(-(-cus // tiles), K // (2 * F8_KT)))
         t = (S, cfg)
     return t if valid(M, N, K, mode, t[0], t[1]) else None
@@ -1034,8 +1036,9 @@ def f8_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, sw: torc
     return _codes_linear("gemm_f8", f8_plan, _f8_valid, a, sx, q, sw, mode, plan, out)
 
 
-def _codes_linear(name: str, plan_of, valid, a, sx, q, sw, mode, plan, out):
-    """The checks and the launch of f8_linear_codes / i8_linear_codes (`name`: the native entry)."""
+def _codes_linear(name: str, plan_of, valid, a, sx, q, sw, mode, plan, out, packed: bool = False):
+    """The checks and the launch of f8_linear_codes / i8_linear_codes / i4_linear_codes (`name`: the
+    native entry; packed: q is [N, K / 2] int4 pairs and sw the [K / 128, N] group scales)."""
     def bad(what):
         return ValueError(f"{name}: {what}")
 
@@ -1048,7 +1051,7 @@ def _codes_linear(name: str, plan_of, valid, a, sx, q, sw, mode, plan, out):
     if not (a.device == q.device == sx.device == sw.device) or not a.is_cuda:
         raise bad("codes and scales must be on one GPU")
     (M, K), N = a.shape, q.shape[0]
-    if q.shape[1] != K or sx.numel() != M or sw.numel() != N:
+    if q.shape[1] * (2 if packed else 1) != K or sx.numel() != M or sw.numel() != (N * (K // WQ_GROUP) if packed else N):
         raise bad(f"a {tuple(a.shape)}, q {tuple(q.shape)}, {sx.numel()} row scales, {sw.numel()} channel scales")
     if mode not in (MODE_BF16, MODE_PARTIAL, MODE_SILU):
         raise bad(f"unknown mode {mode}")
@@ -1143,3 +1146,84 @@ def i8_linear(x: torch.Tensor, q: torch.Tensor, sw: torch.Tensor, mode: int = MO
         raise ValueError(f"gemm_i8: unsupported M={x.shape[0]} N={q.shape[0]} K={x.shape[1]} mode={mode}")
     a, sx = quant_rows_int8(x)
     return i8_linear_codes(a, sx, q, sw, mode, plan, out)
+
+
+# ---------------------------------------------------------------------------- gemm_i4 (int8 codes x int4 codes, M > 320)
+# csrc/kernels/gemm_i4.hip: prompt-sized steps of an int4 model on v_mfma_i32_16x16x64_i8. The
+# activations are quantized per row (token) to int8, the packed weight codes are read as
+# quantize_int4 stores them and widened in registers, every 128-k group is summed in int32 and
+# folded into fp32 with its group scale:
+#   out[m, n] = sx[m] sum_g gs[g, n] (A_g . Q_g^T)[m, n]
+# The kernel takes A in KERNEL ORDER (i4_order): the k order in which the widened weight words
+# come out of the packed ones, so that the GEMM shuffles no bytes. cfg -> (tile rows, LDS ring
+# slots), the mirror of I4_CFGS there; K tile, columns and the row quantizer's K limit are gemm_f8's.
+I4_CFGS = {0: (256, 3), 1: (128, 4)}
+_I4_TUNED = {}     # (N, K, mode) -> {M: (split_k, cfg)}: empty until somebody sweeps it
+# byte b of every 16 consecutive k holds k I4_K_OF[b] (gemm_f8.hip I8CodesI4::K_OF)
+I4_K_OF = (0, 4, 1, 5, 8, 12, 9, 13, 2, 6, 3, 7, 10, 14, 11, 15)
+
+
+def i4_order(codes: torch.Tensor) -> torch.Tensor:
+    """Natural-order row codes [M, K] (K % 16 == 0) -> gemm_i4's kernel order."""
+    M, K = codes.shape
+    if K % 16:
+        raise ValueError(f"i4_order: needs K % 16 == 0, got K={K}")
+    idx = torch.tensor(I4_K_OF, device=codes.device)
+    return codes.view(M, K // 16, 16)[:, :, idx].reshape(M, K).contiguous()
+
+
+def quant_rows_int8_i4(x: torch.Tensor):
+    """(i4_order(codes), sx) of quantize_rows_int8(x), bit for bit: the HIP kernel on a GPU (the
+    int8 row quantizer storing the kernel order), PyTorch elsewhere."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError(f"quant_rows_int8_i4: x must be a contiguous 2-d bfloat16, got {x.dtype} {tuple(x.shape)}")
+    M, K = x.shape
+    if M < 1 or K < 16 or K % 16 or K > F8_QUANT_MAX_K:
+        raise ValueError(f"quant_rows_int8_i4: needs M >= 1, K % 16 == 0, 16 <= K <= {F8_QUANT_MAX_K}, got M={M} K={K}")
+    if not use_native(x):
+        codes, sx = quantize_rows_int8(x)
+        return i4_order(codes), sx
+    codes = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    sx = torch.empty(M, dtype=torch.float32, device=x.device)
+    kernels().quant_rows_int8_i4(x.data_ptr(), M, K, codes.data_ptr(), sx.data_ptr(), stream_ptr())
+    return codes, sx
+
+
+def _i4_valid(M: int, N: int, K: int, mode: int, S: int, cfg: int) -> bool:
+    """gemm_i4.hip i4_supports: whole 256-column tiles, whole 128-k tiles (= scale groups), at least
+    one per split; bf16 / SiLU epilogues at split 1. No bound on K: a sum spans one group."""
+    if M < 1 or cfg not in I4_CFGS:
+        return False
+    if K < F8_KT or K % F8_KT or N < F8_COLS or N % F8_COLS or S < 1 or S > K // F8_KT:
+        return False
+    if -(-M // I4_CFGS[cfg][0]) * (N // F8_COLS) * S >= 1 << 31:
+        return False
+    return mode == MODE_PARTIAL or (mode in (MODE_BF16, MODE_SILU) and S == 1)
+
+
+@functools.lru_cache(maxsize=4096)
+def i4_plan(M: int, N: int, K: int, mode: int = MODE_PARTIAL, cus: int = 256):
+    """(split_k, cfg) for gemm_i4, or None when the shape is unsupported: f8_plan's rule over
+    I4_CFGS and a table of its own, _I4_TUNED (empty)."""
+    return _f8_rule(M, N, K, mode, cus, _I4_TUNED, _i4_valid, I4_CFGS)
+
+
+def i4_linear_codes(a: torch.Tensor, sx: torch.Tensor, q: torch.Tensor, gs: torch.Tensor, mode: int = MODE_PARTIAL,
+                    plan=None, out: Optional[torch.Tensor] = None):
+    """gemm_i4 on codes given: a [M, K] int8 codes as uint8 in kernel order (i4_order), sx [M] fp32;
+    q [N, K / 2] packed int4 codes and gs [K / 128, N] fp32 of quantize_int4. Returns what
+    f8_linear_codes returns: bf16 [M, N] (MODE_BF16), a PendingSum (MODE_PARTIAL) or
+    silu(gate) * up [M, N / 2] of a block-16 interleaved gate|up weight."""
+    return _codes_linear("gemm_i4", i4_plan, _i4_valid, a, sx, q, gs, mode, plan, out, packed=True)
+
+
+def i4_linear(x: torch.Tensor, q: torch.Tensor, gs: torch.Tensor, mode: int = MODE_PARTIAL, plan=None,
+              out: Optional[torch.Tensor] = None):
+    """x bf16 [M, K] quantized per row to int8 in kernel order (quant_rows_int8_i4), then gemm_i4
+    against the int4 weight (q, gs) of quantize_int4: W4A8 with dynamic per-token scales."""
+    if x.dim() != 2 or q.dim() != 2 or x.shape[1] != 2 * q.shape[1] or not x.is_cuda or x.device != q.device:
+        raise ValueError(f"gemm_i4: x {tuple(x.shape)} on {x.device} does not go with q {tuple(q.shape)} on {q.device}")
+    if plan is None and i4_plan(x.shape[0], q.shape[0], x.shape[1], mode, cu_count(x.device)) is None:
+        raise ValueError(f"gemm_i4: unsupported M={x.shape[0]} N={q.shape[0]} K={x.shape[1]} mode={mode}")
+    a, sx = quant_rows_int8_i4(x)
+    return i4_linear_codes(a, sx, q, gs, mode, plan, out)

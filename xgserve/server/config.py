@@ -112,7 +112,8 @@ class WorkerSection:
     # their activations per token to E4M3 and run on the FP8 matrix instructions (gemm_f8), so
     # outputs differ from the weight-only server's; smaller steps stay weight-only
     fp8_activations: bool = False
-    # the same with quantization int8: per-token int8 codes on the INT8 matrix instructions (gemm_i8)
+    # the same with quantization int8 (gemm_i8) or int4 (gemm_i4): per-token int8 codes on the INT8
+    # matrix instructions
     int8_activations: bool = False
     block_size: int = 16
     max_num_seqs: int = 256
@@ -227,11 +228,11 @@ class ServerConfig:
             e.append("worker.quantized_only needs a GPU (worker.device is cpu)")
         if w.fp8_activations and w.int8_activations:
             e.append("worker.fp8_activations and worker.int8_activations exclude each other (one weight format)")
-        for key, need in (("fp8_activations", "fp8"), ("int8_activations", "int8")):
+        for key, need in (("fp8_activations", ("fp8",)), ("int8_activations", ("int8", "int4"))):
             if not getattr(w, key):
                 continue
-            if w.quantization != need:
-                e.append(f"worker.{key} needs worker.quantization {need}, got {w.quantization!r}")
+            if w.quantization not in need:
+                e.append(f"worker.{key} needs worker.quantization {' or '.join(need)}, got {w.quantization!r}")
             if w.device == "cpu":
                 e.append(f"worker.{key} needs a GPU (worker.device is cpu)")
             if w.tp != 1:
