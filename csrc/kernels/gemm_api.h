@@ -138,5 +138,15 @@ int quant_rows_int8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, 
 int gemm_i4(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* gs, int N, float* part,
             uint16_t* out, int S, int mode, int cfg, hipStream_t st);
 int quant_rows_int8_i4(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
+// lm_head_score.hip: per row of h [M, K] (row stride ldh) against the LM head w [>= V, K] (row stride
+// ldw), lp = z[t] - logsumexp(z), best_id = argmax z, best_lp = max z - logsumexp(z) over v < V, from
+// one (max, sum, argmax) partial per BM x BN tile of z = h w^T: no logits are written. targets int32
+// [M], a value outside [0, V) = no target (lp 0); ws holds lm_head_score_ws_floats(M, V) floats.
+// One tile configuration, no plan table. K >= 64, K % 64 == 0, V >= 1, M >= 0 (0 launches nothing)
+int lm_head_score(const uint16_t* h, int64_t ldh, int M, int K, const uint16_t* w, int64_t ldw, int V,
+                  const int32_t* targets, float* ws, float* lp, int32_t* best_id, float* best_lp, hipStream_t st);
+int64_t lm_head_score_ws_floats(int M, int V);
+int lm_head_score_bm();
+int lm_head_score_bn();
 
 }  // namespace xgk

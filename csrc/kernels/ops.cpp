@@ -498,6 +498,23 @@ PYBIND11_MODULE(_kernels, m) {
     check(xgk::quant_rows_int8_i4(P<const uint16_t>(x), M, K, P<uint8_t>(codes), P<float>(sx), S(st)),
           "quant_rows_int8_i4");
   });
+  // lm_head_score.hip: target log-probability, best token and its log-probability per row, from
+  // tile partials of h w^T (no logits buffer). ws: lm_head_score_ws_floats(M, V) floats
+  m.def("lm_head_score", [](uintptr_t h, int64_t ldh, int M, int K, uintptr_t w, int64_t ldw, int V, uintptr_t targets,
+                            uintptr_t ws, uintptr_t lp, uintptr_t best_id, uintptr_t best_lp, uintptr_t st) {
+    if (K < 64 || K % 64) throw std::invalid_argument("lm_head_score: K < 64 or K % 64 != 0");
+    if (V < 1) throw std::invalid_argument("lm_head_score: V < 1");
+    if (M < 0) throw std::invalid_argument("lm_head_score: M < 0");
+    if (M == 0) return;  // nothing to launch: no device call either
+    check(xgk::lm_head_score(P<const uint16_t>(h), ldh, M, K, P<const uint16_t>(w), ldw, V, P<const int32_t>(targets),
+                             P<float>(ws), P<float>(lp), P<int32_t>(best_id), P<float>(best_lp), S(st)),
+          "lm_head_score");
+  });
+  m.def("lm_head_score_ws_floats", [](int M, int V) {
+    if (M < 0 || V < 1) throw std::invalid_argument("lm_head_score_ws_floats: M < 0 or V < 1");
+    return xgk::lm_head_score_ws_floats(M, V);
+  });
+  m.def("lm_head_score_tile", []() { return std::make_pair(xgk::lm_head_score_bm(), xgk::lm_head_score_bn()); });
   m.def("set_pf_krot", [](int on) { xgk::set_pf_krot(on); });
   m.def("set_k_rotation", [](int mode) { xgk::set_k_rotation(mode); });
   m.def("gemm_m64g_ex", [](uintptr_t x, int M, int K, uintptr_t w, int N, uintptr_t part, uintptr_t out, int splits,

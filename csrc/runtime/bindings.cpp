@@ -59,6 +59,7 @@ py::dict plan_dict(const StepPlan& p) {
   d["is_prefill"] = arr(p.is_prefill);
   d["do_sample"] = arr(p.do_sample);
   d["is_embed"] = arr(p.is_embed);
+  d["is_score"] = arr(p.is_score);
   d["input_ids"] = arr(p.input_ids);
   d["positions"] = arr(p.positions);
   d["slot_mapping"] = arr(p.slot_mapping);
@@ -250,7 +251,7 @@ PYBIND11_MODULE(_runtime, m) {
       .def(py::init<const SchedulerConfig&>())
       .def("add", &StepScheduler::add, py::arg("id"), py::arg("prompt"), py::arg("max_tokens"),
            py::arg("priority") = 1, py::arg("ignore_eos") = false, py::arg("embed") = false,
-           py::arg("stop_seqs") = std::vector<std::vector<int32_t>>{}, py::arg("min_tokens") = 0)
+           py::arg("stop_seqs") = std::vector<std::vector<int32_t>>{}, py::arg("min_tokens") = 0, py::arg("score") = false)
       .def("abort", &StepScheduler::abort)
       .def("set_draft", &StepScheduler::set_draft)
       .def("schedule", [](StepScheduler& s) { return plan_dict(s.schedule()); })

@@ -66,7 +66,7 @@ const Sequence* StepScheduler::get(int64_t id) const {
 
 bool StepScheduler::add(int64_t id, const std::vector<int32_t>& prompt, int max_tokens, int priority,
                         bool ignore_eos, bool embed,
-                        const std::vector<std::vector<int32_t>>& stop_seqs, int min_tokens) {
+                        const std::vector<std::vector<int32_t>>& stop_seqs, int min_tokens, bool score) {
   if (seqs_.count(id) || prompt.empty()) return false;
   const int limit = embed ? cfg_.max_model_len : cfg_.max_model_len - 1;
   if (static_cast<int>(prompt.size()) > limit) return false;
@@ -80,6 +80,7 @@ bool StepScheduler::add(int64_t id, const std::vector<int32_t>& prompt, int max_
   s->min_tokens = min_tokens;
   s->ignore_eos = ignore_eos;
   s->embed = embed;
+  s->score = score;
   for (const auto& ss : stop_seqs)
     if (!ss.empty()) s->stop_seqs.push_back(ss);
   Sequence* raw = s.get();
@@ -183,6 +184,7 @@ void StepScheduler::emit(Sequence& s, int q, bool prefill, bool sample) {
   p.is_prefill.push_back(prefill ? 1 : 0);
   p.do_sample.push_back(sample ? 1 : 0);
   p.is_embed.push_back(s.embed ? 1 : 0);
+  p.is_score.push_back(s.score && prefill ? 1 : 0);
   const int n_tok = static_cast<int>(s.tokens.size());
   for (int t = 0; t < q; ++t) {
     int pos = s.num_computed + t;
@@ -297,7 +299,8 @@ const StepPlan& StepScheduler::schedule() {
     if (s->tokens.back() == kPlaceholder) break;  // preempted by a lookahead plan: wait for commit()
     int matched_pages = 0;
     bool looked_up = false;
-    if (cfg_.enable_prefix_cache && s->blocks.empty() && s->num_computed == 0) {
+    // a scored sequence needs every prompt row computed: no lookup (it still publishes its pages)
+    if (cfg_.enable_prefix_cache && !s->score && s->blocks.empty() && s->num_computed == 0) {
       looked_up = true;
       const int n = static_cast<int>(s->tokens.size());
       std::vector<int> pages = cache_.match(s->tokens.data(), n, n - 1, /*count=*/false);
@@ -423,7 +426,7 @@ bool StepScheduler::lookahead(bool across_length_finish) {
   for (int i = 0; i < p.num_seqs; ++i) {
     const Sequence* s = plan_seqs_[i];
     if (s == nullptr) continue;
-    if (!s->draft.empty() || p.is_embed[i]) return false;  // verify / embedding steps stay synchronous
+    if (!s->draft.empty() || p.is_embed[i] || p.is_score[i]) return false;  // verify / embedding / scoring steps stay synchronous
     // a sampled row that reaches its length limit with this token: either released
     // early below, or (the default) this plan stays synchronous
     const int i_sampled = p.do_sample[i];

@@ -86,6 +86,7 @@ struct Sequence {
   int min_tokens = 0;
   bool ignore_eos = false;
   bool embed = false;  // prefill-only (embeddings endpoint)
+  bool score = false;  // prompt scoring: every prompt row is computed (no prefix-cache hit at admission)
   bool released_early = false;  // length-finishing row released at lookahead(); reported at commit()
   int wait_plans = 0;            // plans that passed this waiting prompt over (admission window)
   std::vector<std::vector<int32_t>> stop_seqs;
@@ -107,7 +108,7 @@ struct StepPlan {
   int bt_width = 0;
   std::vector<int64_t> seq_ids;
   std::vector<int32_t> slots, q_lens, ctx_lens, seq_lens;
-  std::vector<uint8_t> is_prefill, do_sample, is_embed;
+  std::vector<uint8_t> is_prefill, do_sample, is_embed, is_score;  // is_score: a prefill chunk of a scored sequence
   std::vector<int32_t> input_ids, positions, slot_mapping, query_start_loc;
   std::vector<int32_t> block_tables;  // [num_seqs, bt_width]
   std::vector<int32_t> logits_indices, sample_seq_index;
@@ -129,7 +130,7 @@ class StepScheduler {
   // returns false if the id is already known or the prompt is too long.
   bool add(int64_t id, const std::vector<int32_t>& prompt, int max_tokens, int priority,
            bool ignore_eos, bool embed, const std::vector<std::vector<int32_t>>& stop_seqs,
-           int min_tokens = 0);
+           int min_tokens = 0, bool score = false);
   bool abort(int64_t id);
   bool set_draft(int64_t id, const std::vector<int32_t>& draft);
 
@@ -149,7 +150,7 @@ class StepScheduler {
   // next plan, whose row for it is then ignored. A row that reaches its length
   // limit with this token is released at once (unless across_length_finish), so
   // the next plan can admit into its slot; commit() reports it. Returns false (and
-  // does nothing) for verify / embedding plans.
+  // does nothing) for verify / embedding / scoring plans.
   static constexpr int32_t kPlaceholder = -1;
   bool lookahead(bool across_length_finish = false);
   std::vector<FinishedSeq> commit(const int32_t* tokens, int num_sample);

@@ -40,7 +40,7 @@ EXTRA_FLAGS = {"gemm_mw8.hip": NO_PACKED_FP32, "moe_gemm_w8.hip": NO_PACKED_FP32
 # Sources whose kernels must not spill: which instantiations exist is decided by a register rule
 # fitted to the compiler (gemm_mw8.hip mw8_regs), so the build reads the compiler's resource report
 # and fails on any scratch instead of trusting the rule.
-NO_SCRATCH = {"gemm_mw8.hip", "moe_gemm_w8.hip", "gemm_f8.hip", "gemm_i4.hip"}
+NO_SCRATCH = {"gemm_mw8.hip", "moe_gemm_w8.hip", "gemm_f8.hip", "gemm_i4.hip", "lm_head_score.hip"}
 RESOURCE_REPORT = ["-Rpass-analysis=kernel-resource-usage"]
 
 

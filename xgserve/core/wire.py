@@ -214,6 +214,16 @@ def _logprobs_flag(d: dict) -> bool:
     return v if isinstance(v, bool) else False
 
 
+def bool_field(d: dict, name: str) -> bool:
+    """`prompt_logprobs` (and the completions alias' `echo`): a boolean; absent or null is false."""
+    v = d.get(name)
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValidationError.invalid_parameter(name, "must be a boolean")
+    return v
+
+
 PROCESSOR_FIELDS = ("top_k", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias")
 
 
@@ -240,6 +250,7 @@ class GenerateRequest:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logit_bias: Dict[int, float] = field(default_factory=dict)
+    prompt_logprobs: bool = False  # score the prompt (raw distribution, at most the best alternative)
 
     @classmethod
     def parse(cls, body: Union[bytes, str, dict]) -> "GenerateRequest":
@@ -256,6 +267,7 @@ class GenerateRequest:
                 raise ValidationError.invalid_json(str(e))
         return cls(prompt=prompt, priority=pr, seed=_opt_int(d, "seed"),
                    logprobs=_logprobs_flag(d), top_logprobs=top_logprobs_field(d),
+                   prompt_logprobs=bool_field(d, "prompt_logprobs"),
                    ignore_eos=d.get("ignore_eos") is True, **s, **_processors(d))
 
 
@@ -284,6 +296,7 @@ class ChatRequest:
     logit_bias: Dict[int, float] = field(default_factory=dict)
     logprobs: bool = False
     top_logprobs: int = 0
+    prompt_logprobs: bool = False
 
     @classmethod
     def parse(cls, body: Union[bytes, str, dict]) -> "ChatRequest":
@@ -294,7 +307,8 @@ class ChatRequest:
             raise ValidationError.invalid_json("invalid type for `messages`: expected a sequence")
         msgs = [ChatMessage.from_dict(m) for m in d["messages"]]
         return cls(messages=msgs, seed=_opt_int(d, "seed"), ignore_eos=d.get("ignore_eos") is True,
-                   logprobs=_logprobs_flag(d), top_logprobs=top_logprobs_field(d), **_sampling(d), **_processors(d))
+                   logprobs=_logprobs_flag(d), top_logprobs=top_logprobs_field(d),
+                   prompt_logprobs=bool_field(d, "prompt_logprobs"), **_sampling(d), **_processors(d))
 
 
 @dataclass
@@ -488,6 +502,9 @@ class TokenEvent:
     # not serialised: (token id, logprob, [(id, logprob)] or None) of every token the event
     # covers, for the OpenAI aliases' per-chunk logprobs objects
     detail: Optional[list] = None
+    # extension, on the done event of a request that asked for prompt scores:
+    # {"tokens", "token_ids", "token_logprobs", "top_logprobs"}; serialised only when present
+    prompt_logprobs: Optional[dict] = None
 
     @classmethod
     def tok(cls, token: str, index: int, logprob: Optional[float] = None,
@@ -495,8 +512,8 @@ class TokenEvent:
         return cls("token", token=token, index=index, logprob=logprob, top_logprobs=top_logprobs)
 
     @classmethod
-    def done(cls, finish_reason: FinishReason, usage: Usage) -> "TokenEvent":
-        return cls("done", finish_reason=finish_reason, usage=usage)
+    def done(cls, finish_reason: FinishReason, usage: Usage, prompt_logprobs: Optional[dict] = None) -> "TokenEvent":
+        return cls("done", finish_reason=finish_reason, usage=usage, prompt_logprobs=prompt_logprobs)
 
     @classmethod
     def error(cls, message: str, code: str) -> "TokenEvent":
@@ -511,8 +528,10 @@ class TokenEvent:
                 d["top_logprobs"] = self.top_logprobs
             return d
         if self.type == "done":
-            return {"type": "done", "finish_reason": self.finish_reason.value,
-                    "usage": self.usage.to_dict()}
+            d = {"type": "done", "finish_reason": self.finish_reason.value, "usage": self.usage.to_dict()}
+            if self.prompt_logprobs is not None:
+                d["prompt_logprobs"] = self.prompt_logprobs
+            return d
         return {"type": "error", "message": self.message, "code": self.code}
 
     @classmethod
@@ -521,7 +540,7 @@ class TokenEvent:
         if t == "token":
             return cls.tok(d["token"], d["index"], d.get("logprob"), d.get("top_logprobs"))
         if t == "done":
-            return cls.done(FinishReason(d["finish_reason"]), Usage.from_dict(d["usage"]))
+            return cls.done(FinishReason(d["finish_reason"]), Usage.from_dict(d["usage"]), d.get("prompt_logprobs"))
         if t == "error":
             return cls.error(d.get("message", d.get("messages")), d["code"])
         raise ValueError(f"unknown TokenEvent type {t!r}")

@@ -339,9 +339,22 @@ class LLMEngine:
                     or not 0 <= params.top_logprobs <= TOPLP_MAX:
                 raise UnsupportedSampling("top_logprobs", f"must be an integer between 0 and {TOPLP_MAX}")
             params.logprobs = True
+        score = False
+        if params.prompt_logprobs is not False:
+            if not isinstance(params.prompt_logprobs, bool):
+                raise UnsupportedSampling("prompt_logprobs", "must be a boolean")
+            if get_state().tp_size > 1:
+                raise UnsupportedSampling("prompt_logprobs", "is not supported with tensor parallelism")
+            if self.spec is not None:
+                raise UnsupportedSampling("prompt_logprobs", "is not supported together with speculative decoding")
+            score = kind != RequestType.Embeddings
         max_tokens = params.max_tokens
         if kind != RequestType.Embeddings:
             max_tokens = min(max_tokens, self.max_model_len - len(prompt_ids))
+        # scoring only (max_tokens = 0): the scheduler runs the prompt and one sampled token, which is dropped
+        score_only = score and params.max_tokens == 0
+        if score_only:
+            max_tokens = 1
         if kind != RequestType.Embeddings and len(prompt_ids) >= self.max_model_len:
             raise ValueError(f"prompt of {len(prompt_ids)} tokens exceeds max_model_len={self.max_model_len}")
         if kind == RequestType.Embeddings and len(prompt_ids) > self.max_model_len:
@@ -350,11 +363,15 @@ class LLMEngine:
         req = EngineRequest(request_id=request_id, seq_id=seq_id, prompt_ids=prompt_ids, params=params,
                             priority=priority, kind=kind, user_data=user_data)
         req.detok = IncrementalDetokenizer(self.tokenizer, params.stop)
+        if score:
+            req.prompt_scores = [None] * len(prompt_ids)
         if params.seed is None:
             params.seed = (hash(request_id) ^ (seq_id * 0x9E3779B97F4A7C15)) & _MASK63
         with self._lock:
-            ok = self.sched.add(seq_id, prompt_ids, max(0, max_tokens), priority, params.ignore_eos,
-                                kind == RequestType.Embeddings, params.stop_token_ids, params.min_tokens)
+            # scoring only: nothing may stop the dropped token's step but its length (finish reason "length")
+            ok = self.sched.add(seq_id, prompt_ids, max(0, max_tokens), priority, params.ignore_eos or score_only,
+                                kind == RequestType.Embeddings, [] if score_only else params.stop_token_ids,
+                                0 if score_only else params.min_tokens, score)
             if not ok:
                 raise ValueError("scheduler rejected the request (duplicate id or too long)")
             self.requests[request_id] = req
@@ -568,8 +585,43 @@ class LLMEngine:
             raise RuntimeError("async scheduling: placeholder without a producing row")
         return np.where(need, j, -1).astype(np.int32)
 
+    def _score_request(self, plan) -> None:
+        """plan["_score"] = (rows, targets) over the prompt rows of the plan's scored chunks: the row
+        at prompt position p is scored against prompt[p + 1] (-1 for the last prompt row, which the
+        sampler handles; the target of a chunk's last row is the next chunk's first token). Rows past
+        the prompt (a recomputed sequence) are left out. plan["_score_dest"]: (request, first
+        position, rows) per chunk, in row order."""
+        rows, targets, dest = [], [], []
+        for i in np.nonzero(plan["is_score"])[0].tolist():
+            req = self.by_seq.get(int(plan["seq_ids"][i]))
+            if req is None or req.prompt_scores is None:
+                continue
+            a, p0, P = int(plan["query_start_loc"][i]), int(plan["ctx_lens"][i]), len(req.prompt_ids)
+            n = min(int(plan["q_lens"][i]), P - p0)
+            if n <= 0:
+                continue
+            rows.extend(range(a, a + n))
+            targets.extend(req.prompt_ids[p0 + 1:p0 + n + 1] + ([-1] if p0 + n == P else []))
+            dest.append((req, p0, n))
+        if rows:
+            plan["_score"] = (np.asarray(rows, np.int32), np.asarray(targets, np.int32))
+            plan["_score_dest"] = dest
+
+    def _store_scores(self, plan) -> None:
+        """A step's scores onto their requests, by prompt position: entry p + 1 comes from row p
+        (a recomputed row overwrites itself)."""
+        lp, best_id, best_lp = plan["_score_out"]
+        k = 0
+        for req, p0, n in plan["_score_dest"]:
+            for r in range(n):
+                if p0 + r + 1 < len(req.prompt_ids):
+                    req.prompt_scores[p0 + r + 1] = (float(lp[k + r]), int(best_id[k + r]), float(best_lp[k + r]))
+            k += n
+
     def _launch(self, plan, samp, src=None):
         """runner.launch on every TP rank: followers receive the same launch."""
+        if plan["is_score"].any():
+            self._score_request(plan)
         if get_state().tp_size > 1:
             comm.tp_broadcast_object(("launch", (plan, samp, src)), src=0)
         return self.runner.launch(plan, samp, src=src)
@@ -619,6 +671,7 @@ class LLMEngine:
         toks, lps, hidden = self.runner.wait(handle)
         plan["_t_tokens"] = time.monotonic()
         plan["_top"] = self.runner.top_result
+        plan["_score_out"] = self.runner.score_result
         t = self._tick("wait_gpu", t)
         n_sample = int(plan["num_sample"])
         counts = np.ones(n_sample, np.int32)
@@ -668,6 +721,8 @@ class LLMEngine:
             toks, lps, hidden, counts = self.spec.verify_execute(plan, samp)
             plan["_t_tokens"] = time.monotonic()
         else:
+            if self.is_driver and plan["is_score"].any():
+                self._score_request(plan)
             handle = self.runner.launch(plan, samp)
             t = self._tick("launch", t)
             outs += self._emit_early(self._flush_deferred())  # previous step's outputs, while this one runs
@@ -675,6 +730,7 @@ class LLMEngine:
             toks, lps, hidden = self.runner.wait(handle)
             plan["_t_tokens"] = time.monotonic()
             plan["_top"] = self.runner.top_result
+            plan["_score_out"] = self.runner.score_result
             t = self._tick("wait_gpu", t)
         if counts is None:
             counts = np.ones(int(plan["num_sample"]), np.int32)
@@ -693,6 +749,8 @@ class LLMEngine:
         self.stats_counters["prefill_tokens_computed"] += int(plan["num_tokens"]) - int(plan["num_decodes"])
         if hidden is not None:
             self._accumulate_embeddings(plan, hidden)
+        if plan.get("_score_out") is not None:
+            self._store_scores(plan)
         n_sample = int(plan["num_sample"])
         if fin_map is None:
             fin_map = self._apply(plan, toks, counts)
@@ -818,6 +876,11 @@ class LLMEngine:
                 kk = req.params.top_logprobs
                 new_top = [[(int(i), float(l)) for i, l in (row or [])[:kk] if i >= 0] for row in tops[k:k + take]]
             k += c
+            scores = None
+            if req.prompt_scores is not None and req.first_token_time is None:
+                scores = list(req.prompt_scores)  # the prompt completed with this step: every row is in
+                if req.params.max_tokens == 0:    # scoring only: the sampled token is not part of the answer
+                    new, new_lps, new_top = [], ([] if new_lps is not None else None), ([] if new_top is not None else None)
             if req.first_token_time is None:
                 req.first_token_time = now
             req.output_ids.extend(new)
@@ -834,7 +897,7 @@ class LLMEngine:
             out = RequestOutput(req.request_id, new, text, reason is not None,
                                 FINISH_NAMES.get(reason) if reason else None,
                                 prompt_tokens=len(req.prompt_ids), completion_tokens=len(req.output_ids),
-                                logprobs=new_lps, t_tokens=t_tok, top_logprobs=new_top)
+                                logprobs=new_lps, t_tokens=t_tok, top_logprobs=new_top, prompt_logprobs=scores)
             if reason is not None:
                 out.cached_tokens = req.cached_tokens
                 self._finish(req, reason)

@@ -39,6 +39,9 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logit_bias: Dict[int, float] = field(default_factory=dict)
+    # score the prompt: log p(prompt[i] | prompt[:i]) and the best token of every position, of the raw
+    # (temperature 1, unprocessed) distribution; with it max_tokens = 0 is allowed (scoring only)
+    prompt_logprobs: bool = False
 
     @property
     def needs_counts(self) -> bool:
@@ -92,6 +95,9 @@ class RequestOutput:
     # per new token, the `top_logprobs` most likely (token id, logprob) pairs, best first
     # (SamplingParams.top_logprobs > 0; entries the row did not have are left out)
     top_logprobs: Optional[List[List[Tuple[int, float]]]] = None
+    # SamplingParams.prompt_logprobs, on the request's first output: one entry per prompt token, None
+    # for the first, else (logprob of the token, best token id, logprob of the best token)
+    prompt_logprobs: Optional[List[Optional[Tuple[float, int, float]]]] = None
 
 
 @dataclass
@@ -111,6 +117,7 @@ class EngineRequest:
     finish_reason: Optional[str] = None
     cached_tokens: int = 0
     embed_acc_row: int = -1
+    prompt_scores: Optional[List[Optional[Tuple[float, int, float]]]] = None  # by prompt position
     user_data: Any = None
 
     @property

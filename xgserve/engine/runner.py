@@ -136,6 +136,7 @@ class StepHandle:
     follower_event: Optional[object] = None  # a step of a TP follower: no D2H, an event of this step only
     top: Optional[TopRecord] = None
     spec: Optional[SpecRecord] = None
+    score: Optional[tuple] = None           # (lp, best_id, best_lp) of the step's scored prompt rows, on the device
 
 
 class OutputSet:
@@ -256,6 +257,8 @@ class ModelRunner:
         # speculative sampling: accepted[j] of the step's sampled verify blocks, riding the
         # step's output set and event like the top-N results (nothing exists until a step asks)
         self.spec_result = None       # int32 per sampled block of the step wait() last returned, or None
+        # prompt scoring: (lp, best_id, best_lp) numpy, one entry per row of the plan's "_score" request
+        self.score_result = None
         self.sampler_logits = None    # what the last step's sampler read, in sample order
         self.keep_sampler_logits = False  # eager steps too (a speculating draft): holds the tensor a step longer
         # eager-step sampling rows (units: rows): temperatures | top-p, top-k, seeds, and the
@@ -720,6 +723,8 @@ class ModelRunner:
             if self._warm_launches == 0:
                 self._set_comm_timeout(self.collective_timeout_s)
         need_hidden = bool(plan["is_embed"].any()) if ns else False
+        if plan.get("_score") is not None:  # scored prompt rows: the eager step scores them behind its forward
+            return self._execute_eager(plan, samp, need_hidden, src)
         bucket = self._graph_bucket(Nd) if (Nd == ns and T == Nd and not need_hidden) else None
         if bucket is not None and self.graphs:
             return self._execute_graph(plan, samp, Nd, bucket, src)
@@ -793,6 +798,8 @@ class ModelRunner:
         res = self._wait(handle)
         self.top_result = self._top_collect(handle) if handle.top is not None else None
         self.spec_result = self._spec_collect(handle) if handle.spec is not None else None
+        # queued ahead of the step's event (a step that samples nothing: this copy waits for it)
+        self.score_result = tuple(t.cpu().numpy() for t in handle.score) if handle.score is not None else None
         return res
 
     def _wait(self, h: StepHandle):
@@ -1021,12 +1028,13 @@ class ModelRunner:
                         pre_max_q=int(plan["q_lens"][Nd:].max()) if Np > 0 else 0)
         h = self.model(ids, meta, self.kv_caches)
         hid = h if need_hidden else None
+        score = self._score_rows(h, plan["_score"]) if plan.get("_score") is not None else None
         if S == 0:
-            return StepHandle(hidden=hid, ready=(np.zeros(0, np.int32), np.zeros(0, np.float32), hid))
+            return StepHandle(hidden=hid, ready=(np.zeros(0, np.int32), np.zeros(0, np.float32), hid), score=score)
         logits = self.model.compute_logits(h.index_select(0, lidx.long()))
         if self.capture_logits:
             self.last_logits = logits.float().cpu()
-        hd = StepHandle(n=S, hidden=hid, out=self._acquire_out() if self.is_driver else None)
+        hd = StepHandle(n=S, hidden=hid, out=self._acquire_out() if self.is_driver else None, score=score)
         if not self.is_cuda:
             if self.is_driver:
                 tok, lp = self._sample(logits, samp, hd)
@@ -1050,6 +1058,15 @@ class ModelRunner:
             self.g_out_tok[:S].copy_(tok[:S])
             self._log_samples(S)
         return self._record_out(hd, tok, lp) if self.is_driver else self._follower_out(hd)
+
+    def _score_rows(self, h: torch.Tensor, req: tuple):
+        """ops.score_rows over the step's scored prompt rows: req = (rows of h, target token per row)."""
+        rows, targets = req
+        a = int(rows[0])
+        hs = h[a:a + len(rows)] if bool((np.diff(rows) == 1).all()) else \
+            h.index_select(0, torch.from_numpy(rows.astype(np.int64)).to(h.device))
+        return ops.score_rows(hs, self.model.lm_head_weight(), self.model.cfg.vocab_size,
+                              torch.from_numpy(targets).to(h.device))
 
     def _stage_eager_sampling(self, samp: SamplingRows, n: int, with_proc: bool):
         """An eager step's sampling rows (with_proc: and its processor rows) through the
@@ -1132,5 +1149,5 @@ class ModelRunner:
     def _async_ok(self, S: int, plan: dict) -> bool:
         """May an eager step's successor be planned before its tokens reach the host?
         The same answer on every TP rank (it depends on the plan only)."""
-        return not (not ASYNC_MIXED or not self.graphs or S > self.g_B or bool(plan["is_embed"].any())
+        return not (not ASYNC_MIXED or not self.graphs or S > self.g_B or bool(plan["is_embed"].any()) or plan.get("_score") is not None
                     or int(plan["num_sample"]) != S)

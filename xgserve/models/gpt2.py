@@ -82,6 +82,9 @@ class GPT2ForCausalLM(nn.Module):
             x = layer(x, meta, kv_caches[i], self.cos_sin)
         return ops.layernorm(x, self.lnf_w, self.lnf_b, self.cfg.norm_eps)
 
+    def lm_head_weight(self) -> torch.Tensor:
+        return self.wte
+
     def compute_logits(self, h: torch.Tensor) -> torch.Tensor:
         return F.linear(h, self.wte)
 

@@ -879,6 +879,10 @@ class LlamaForCausalLM(nn.Module):
         hs, _ = ops.fused_add_rmsnorm(xs, residual, self.norm, self.cfg.norm_eps)
         return comm.tp_all_gather_rows(hs)[:T]
 
+    def lm_head_weight(self) -> torch.Tensor:
+        """[>= vocab_size, H] (TP = 1): what ops.score_rows reads"""
+        return self.embed if self.lm_head is None else self.lm_head
+
     def compute_logits(self, h: torch.Tensor) -> torch.Tensor:
         w = self.embed if self.lm_head is None else self.lm_head
         logits = lm_head_linear(h, w)

@@ -18,6 +18,7 @@ from .sampling import (process_logits, process_scratch, logit_state_alloc, logit
                        logit_state_update, logit_state_add, check_hist_pos, pack_state_resets, LOGIT_BIAS_MAX,
                        LOGIT_HIST_MAX)
 from .embedding import embed_gather, mean_l2norm_rows
+from .score import score_rows
 from .moe import (moe_topk_softmax, moe_route, moe_route_norm, moe_align, moe_forward_ref, fused_moe, ep_plan,
                   ep_scatter, ep_combine)
 from ._native import available as native_available
@@ -33,6 +34,7 @@ __all__ = [
     "process_logits", "process_scratch", "logit_state_alloc", "logit_state_cells", "logit_state_reset",
     "logit_state_update", "logit_state_add", "check_hist_pos", "pack_state_resets", "LOGIT_BIAS_MAX", "LOGIT_HIST_MAX",
     "embed_gather", "mean_l2norm_rows",
+    "score_rows",
     "moe_topk_softmax", "moe_route", "moe_route_norm", "moe_align", "moe_forward_ref", "fused_moe", "ep_plan", "ep_scatter", "ep_combine",
     "native_available",
 ]

@@ -32,10 +32,11 @@ from ..core.errors import ApiError, ApiInternal, ApiValidationError, ConfigError
 from ..core.types import Priority
 from ..core.wire import (ChatChoice, ChatMessage, ChatRequest, ChatResponse, EmbeddingData, EmbeddingsRequest,
                          EmbeddingsResponse, FinishReason, GenerateChoice, GenerateRequest, GenerateResponse, Role,
-                         PROCESSOR_FIELDS, TokenEvent, Usage, top_logprobs_field)
+                         PROCESSOR_FIELDS, TokenEvent, Usage, bool_field, top_logprobs_field)
 from ..engine.request import RequestType, SamplingParams
 from ..obs import trace
 from .orchestrator import InferenceServer, ServerRequest, sse_chunk
+from .replica import prompt_logprob_dict
 
 log = logging.getLogger("xgserve.http")
 
@@ -104,7 +105,15 @@ def _params(max_tokens, temperature, top_p, stop, seed=None, ignore_eos=False, l
         sp.logit_bias = dict(req.logit_bias)
         sp.top_logprobs = int(req.top_logprobs)
         sp.logprobs = bool(sp.logprobs or req.logprobs or sp.top_logprobs > 0)
+        sp.prompt_logprobs = bool(req.prompt_logprobs)
     return sp
+
+
+def _check_score_only(sp: SamplingParams) -> None:
+    """/generate and /chat: `prompt_logprobs` does not change what `max_tokens: 0` means there (the
+    engine's scoring-only form belongs to `echo` on /v1/completions), so the pair is a 400."""
+    if sp.prompt_logprobs and sp.max_tokens == 0:
+        raise ValidationError.invalid_parameter("max_tokens", "must be at least 1 with prompt_logprobs")
 
 
 def _tok_text(srv, tid: int) -> str:
@@ -267,6 +276,7 @@ async def handle_generate(request: web.Request) -> web.StreamResponse:
     ids = srv.encode(req.prompt)
     sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req.logprobs,
                  req=req)
+    _check_score_only(sp)
     sreq = await srv.aadmit(RequestType.Generate, ids, sp, req.priority if req.priority is not None else Priority.Normal,
                      stream=req.stream, sse_native=req.stream)
     if req.stream:
@@ -276,6 +286,8 @@ async def handle_generate(request: web.Request) -> web.StreamResponse:
     out = resp.to_dict()
     if sp.logprobs:
         out["choices"][0]["logprobs"] = _lp_native(srv, *_result_lp(r))
+    if sp.prompt_logprobs:
+        out["prompt_logprobs"] = prompt_logprob_dict(srv.tokenizer, ids, r.prompt_logprobs)
     return _json(out)
 
 
@@ -288,6 +300,7 @@ async def handle_chat(request: web.Request) -> web.StreamResponse:
     ids = srv.encode(srv.tokenizer.apply_chat_template(req.messages))
     sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, req.ignore_eos, req.logprobs,
                  req=req)
+    _check_score_only(sp)
     sreq = await srv.aadmit(RequestType.Chat, ids, sp, Priority.Normal, stream=req.stream, sse_native=req.stream)
     if req.stream:
         return await _sse(request, srv, sreq)
@@ -297,6 +310,8 @@ async def handle_chat(request: web.Request) -> web.StreamResponse:
     out = resp.to_dict()
     if sp.logprobs:
         out["choices"][0]["logprobs"] = _lp_native(srv, *_result_lp(r))
+    if sp.prompt_logprobs:
+        out["prompt_logprobs"] = prompt_logprob_dict(srv.tokenizer, ids, r.prompt_logprobs)
     return _json(out)
 
 
@@ -429,12 +444,17 @@ async def handle_v1_completions(request: web.Request) -> web.StreamResponse:
     if d.get("logprobs") is not None:  # OpenAI: an integer, the number of alternatives (0: the token's own only)
         body["top_logprobs"] = top_logprobs_field(d, "logprobs")
         body["logprobs"] = True
+    echo = bool_field(d, "echo")  # prompt + completion; with `logprobs` the prompt's tokens lead the arrays
     req = GenerateRequest.parse(body)
     srv.validate_generate(req.prompt, req.max_tokens, req.temperature, req.top_p)
     _validate_processors(srv, req)
+    if echo and req.stream:
+        raise ValidationError.invalid_parameter("echo", "is not supported together with stream")
     sp = _params(req.max_tokens, req.temperature, req.top_p, req.stop_sequences, req.seed, logprobs=req.logprobs,
                  req=req)
-    sreq = await srv.aadmit(RequestType.Generate, srv.encode(req.prompt), sp,
+    sp.prompt_logprobs = echo  # also what lets max_tokens: 0 finish after the prompt (scoring only)
+    ids = srv.encode(req.prompt)
+    sreq = await srv.aadmit(RequestType.Generate, ids, sp,
                      req.priority if req.priority is not None else Priority.Normal, stream=req.stream)
     created = int(time.time())
     if req.stream:
@@ -457,8 +477,18 @@ async def handle_v1_completions(request: web.Request) -> web.StreamResponse:
                                  rid=r.id).to_dict()
     out["choices"][0]["finish_reason"] = "stop" if r.finish_reason == FinishReason.StopSequence else \
         r.finish_reason.value
+    if echo:
+        out["choices"][0]["text"] = req.prompt + r.text
     if sp.logprobs:
-        out["choices"][0]["logprobs"] = _lp_completions(srv, *_result_lp(r))
+        lp = _lp_completions(srv, *_result_lp(r))
+        if echo:  # as at OpenAI: the first position has no score; at most the best token per prompt position
+            sc = r.prompt_logprobs
+            head = _lp_completions(srv, ids, [0.0 if s is None else s[0] for s in sc],
+                                   [[(s[1], s[2])] if s is not None and req.top_logprobs > 0 else [] for s in sc])
+            head["token_logprobs"][0] = head["top_logprobs"][0] = None
+            tail = _lp_completions(srv, *_result_lp(r), offset=sum(len(t) for t in head["tokens"]))
+            lp = {k: head[k] + tail[k] for k in head}
+        out["choices"][0]["logprobs"] = lp
     return _json(out)
 
 

@@ -38,7 +38,7 @@ from ..router import Router
 from .batcher import RequestBatcher
 from .config import ServerConfig, apply_hot_reload
 from .degradation import DegradationLevel
-from .replica import InProcessReplica, ProcessReplica, Replica, engine_spec, top_logprob_dicts
+from .replica import InProcessReplica, ProcessReplica, Replica, engine_spec, prompt_logprob_dict, top_logprob_dicts
 from .streamer import StreamSender, TokenStreamer
 
 log = logging.getLogger("xgserve.server")
@@ -107,15 +107,15 @@ def ev_to_tuple(ev: TokenEvent) -> tuple:
     u = ev.usage
     return (ev.type, ev.token, ev.index, ev.logprob, ev.finish_reason.value if ev.finish_reason else None,
             (u.prompt_tokens, u.completion_tokens) if u is not None else None, ev.message, ev.code,
-            ev.top_logprobs, ev.detail)
+            ev.top_logprobs, ev.detail, ev.prompt_logprobs)
 
 
 def ev_from_tuple(t: tuple) -> TokenEvent:
-    typ, token, index, logprob, fr, u, message, code, top, detail = t
+    typ, token, index, logprob, fr, u, message, code, top, detail, plp = t
     return TokenEvent(typ, token=token, index=index, logprob=logprob,
                       finish_reason=FinishReason(fr) if fr is not None else None,
                       usage=Usage.new(*u) if u is not None else None, message=message, code=code,
-                      top_logprobs=top, detail=detail)
+                      top_logprobs=top, detail=detail, prompt_logprobs=plp)
 
 
 class ServerRequest:
@@ -145,6 +145,7 @@ class ServerRequest:
         # token's alternatives [(id, logprob)]
         self.lp_token_ids: List[int] = []
         self.top_logprobs: List[list] = []
+        self.prompt_logprobs: Optional[list] = None  # RequestOutput.prompt_logprobs of a scored request
         self.pending_detail: list = []  # OpenAI-alias streams: tokens not yet attached to an event
         self.completion_tokens = 0
         self.cached_tokens = 0
@@ -601,6 +602,8 @@ class InferenceServer:
                     n_wire += 1
                     t_wire = o.t_tokens
                 continue
+            if o.prompt_logprobs is not None:
+                sreq.prompt_logprobs = o.prompt_logprobs
             if o.error:
                 self._finalize(sreq)
                 self.metrics.record_error(o.error_code or "inference_failed")
@@ -711,7 +714,10 @@ class InferenceServer:
         trace.end_span(sreq.espan, completion_tokens=sreq.completion_tokens, finish=sreq.finish_reason.value)
         if sreq.sender is not None:
             try:
-                self.streamer.close_stream(sreq.id, sreq.finish_reason, sreq.usage())
+                plp = None
+                if sreq.prompt_logprobs is not None:
+                    plp = prompt_logprob_dict(self.tokenizer, sreq.prompt_ids, sreq.prompt_logprobs)
+                self.streamer.close_stream(sreq.id, sreq.finish_reason, sreq.usage(), plp)
             except Exception:
                 pass
         elif sreq.future is not None and not sreq.future.done():

@@ -111,6 +111,15 @@ def top_logprob_dicts(tokenizer, top) -> list:
     return [{"token": tokenizer.decode([i]), "token_id": i, "logprob": lp} for i, lp in top]
 
 
+def prompt_logprob_dict(tokenizer, ids, scores) -> dict:
+    """RequestOutput.prompt_logprobs of the prompt `ids` -> the wire object of /generate and /chat:
+    the first position has no score (null, no alternative); the others carry the best token."""
+    ent = [None if s is None else {"token": tokenizer.decode([s[1]]), "token_id": s[1], "logprob": s[2]} for s in scores]
+    return {"tokens": [tokenizer.decode([int(t)]) for t in ids], "token_ids": [int(t) for t in ids],
+            "token_logprobs": [None if s is None else s[0] for s in scores],
+            "top_logprobs": [[] if e is None else [e] for e in ent]}
+
+
 def encode_sse_chunk(text: str, index: int, logprob: Optional[float] = None, top: Optional[list] = None) -> bytes:
     """One native SSE token event (byte-identical to core.wire.TokenEvent.tok(...).sse())
     framed as an HTTP/1.1 chunk, ready for the client socket. top: top_logprob_dicts(...)."""

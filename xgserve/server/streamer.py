@@ -90,11 +90,11 @@ class TokenStreamer:
             raise StreamNotFound(rid)
         s.send(TokenEvent.tok(token, index, logprob))
 
-    def close_stream(self, rid: str, finish_reason: FinishReason, usage: Usage) -> None:
+    def close_stream(self, rid: str, finish_reason: FinishReason, usage: Usage, prompt_logprobs=None) -> None:
         s = self._senders.pop(rid, None)
         if s is None:
             raise StreamNotFound(rid)
-        s.send(TokenEvent.done(finish_reason, usage))
+        s.send(TokenEvent.done(finish_reason, usage, prompt_logprobs))
         s.close()
 
     def fail_stream(self, rid: str, message: str, code: str) -> None:
