@@ -48,18 +48,19 @@ def bench_attn(L, Hq, Hkv, D, gh, iters=20, bs=16):
 
 
 def ttft(L, quantization=None, quantized_only=False, batch=0, batch_prompt_len=512, batch_out=64, default_graphs=False,
-         fp8_activations=False, int8_activations=False):
+         fp8_activations=False, int8_activations=False, model="llama3-8b", fp8_expert_activations=False):
     from xgserve.engine import EngineConfig, LLMEngine, SamplingParams
     wdt = quantization if quantization in ("fp8", "int8", "int4") else None
     # default_graphs: the engine's own decode graph sizes (up to max_num_seqs; above 64 rows too)
     bs = None if default_graphs else sorted({1, *(b for b in (2, 4, 8, 16, 32, 64) if b <= batch)})
-    eng = LLMEngine(EngineConfig(model="llama3-8b", max_num_seqs=max(4, batch), max_num_batched_tokens=max(8192, L),
+    eng = LLMEngine(EngineConfig(model=model, max_num_seqs=max(4, batch), max_num_batched_tokens=max(8192, L),
                                  max_model_len=max(L, batch_prompt_len + batch_out) + 16, graph_batch_sizes=bs,
                                  weight_dtype=wdt, quantized_only=quantized_only,
-                                 fp8_activations=fp8_activations, int8_activations=int8_activations))
+                                 fp8_activations=fp8_activations, int8_activations=int8_activations,
+                                 fp8_expert_activations=fp8_expert_activations))
     res = []
     for it in range(4):
-        prompt = torch.randint(10, 128000, (L,)).tolist()
+        prompt = torch.randint(10, min(128000, eng.mcfg.vocab_size), (L,)).tolist()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         eng.add_request(f"t{it}", prompt, SamplingParams(max_tokens=1, temperature=0.0, ignore_eos=True))
@@ -75,7 +76,7 @@ def ttft(L, quantization=None, quantized_only=False, batch=0, batch_prompt_len=5
     if batch > 0:
         sp = SamplingParams(max_tokens=batch_out, temperature=0.0, ignore_eos=True)
         for it in range(2):  # the second run is the measured one
-            prompts = [torch.randint(10, 128000, (batch_prompt_len,)).tolist() for _ in range(batch)]
+            prompts = [torch.randint(10, min(128000, eng.mcfg.vocab_size), (batch_prompt_len,)).tolist() for _ in range(batch)]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             outs = eng.generate(prompts, sp)
@@ -110,6 +111,10 @@ def main():
                     help="with --quantization int8 / int4: prompt steps above 320 rows on gemm_i8 / gemm_i4 (activations quantized per token)")
     ap.add_argument("--int8-activations-pair", action="store_true",
                     help="with --quantization int8 / int4: the TTFT without and then with int8 activations, in this one call")
+    ap.add_argument("--model", default="llama3-8b", help="the TTFT runs' model (mixtral-8x7b for the expert pair)")
+    ap.add_argument("--fp8-expert-activations-pair", action="store_true",
+                    help="with --quantization fp8 --model mixtral-8x7b: the TTFT without and then with fp8 expert "
+                         "activations (moe_gemm_f8), in this one call")
     a = ap.parse_args()
     kernels()
     for name, Hq, Hkv in (("llama3-8b", 32, 8), ("llama3-70b", 64, 8)):
@@ -118,15 +123,17 @@ def main():
                 us, tf = bench_attn(L, Hq, Hkv, 128, gh)
                 print(json.dumps({"op": "prefill_attention", "heads": name, "L": L, "gh": gh, "us": round(us, 1),
                                   "TFLOP/s": round(tf, 1)}), flush=True)
-    runs = ([(False, False), (True, False)] if a.fp8_activations_pair else
-            [(False, False), (False, True)] if a.int8_activations_pair else [(a.fp8_activations, a.int8_activations)])
-    for a8, ai8 in ([] if a.no_ttft else runs):
+    runs = ([(False, False, False), (False, False, True)] if a.fp8_expert_activations_pair else
+            [(False, False, False), (True, False, False)] if a.fp8_activations_pair else
+            [(False, False, False), (False, True, False)] if a.int8_activations_pair else
+            [(a.fp8_activations, a.int8_activations, False)])
+    for a8, ai8, ea8 in ([] if a.no_ttft else runs):
         r, extra = ttft(a.ttft_len, a.quantization, a.quantized_only, a.batch, a.batch_prompt_len, a.batch_out,
-                        a.default_graphs, a8, ai8)
+                        a.default_graphs, a8, ai8, a.model, ea8)
         torch.cuda.empty_cache()
-        print(json.dumps({"op": "ttft_batch1", "model": "llama3-8b", "prompt_len": a.ttft_len,
+        print(json.dumps({"op": "ttft_batch1", "model": a.model, "prompt_len": a.ttft_len,
                           "quantization": a.quantization, "quantized_only": a.quantized_only, "fp8_activations": a8,
-                          "int8_activations": ai8,
+                          "int8_activations": ai8, "fp8_expert_activations": ea8,
                           "ttft_ms": [round(x, 2) for x in r], "ttft_ms_best_of_last3": round(min(r[1:]), 2),
                           **extra}), flush=True)
 

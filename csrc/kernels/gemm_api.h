@@ -68,6 +68,7 @@ bool mw8_supports(int M, int K, int N, int S, int mode, int cfg, int fmt);
 bool pf_supports(int M, int K, int N, int S, int mode, int cfg);
 bool pf_grouped_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg);
 bool f8_supports(int M, int K, int N, int S, int mode, int cfg);
+bool moe_f8_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg);
 bool i8_supports(int M, int K, int N, int S, int mode, int cfg);  // f8_supports and K <= 131,072
 bool i4_supports(int M, int K, int N, int S, int mode, int cfg);
 
@@ -126,6 +127,12 @@ void set_pf_krot(int on);
 int gemm_f8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,
             uint16_t* out, int S, int mode, int cfg, hipStream_t st);
 int quant_rows_fp8(const uint16_t* x, int M, int K, uint8_t* codes, float* sx, hipStream_t st);
+// its grouped form over moe_align's expert-sorted rows (the prompt-sized expert GEMMs on fp8 expert
+// codes): w [E, N, K], sw [E, N]; rows gathers a and sx (nullptr: both are in sorted order);
+// F8_SILU -> out [P, N / 2], F8_PARTIAL -> part [S, P, N]
+int moe_gemm_f8(const uint8_t* a, const float* sx, const int32_t* rows, const int32_t* offs, int E, int P, int K,
+                const uint8_t* w, const float* sw, int N, int max_pairs, float* part, uint16_t* out, int S, int mode,
+                int cfg, hipStream_t st);
 // the same kernel on int8 codes (w as quantize_int8 stores it) and v_mfma_i32_16x16x64_i8: int32 sums,
 // converted once per split; quant_rows_int8 makes (a, sx) with round-half-even codes in -127 .. 127
 int gemm_i8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, const float* sw, int N, float* part,

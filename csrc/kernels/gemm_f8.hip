@@ -4,6 +4,8 @@
 //   quant_rows_fp8:  x bf16 [M, K]  ->  codes E4M3 [M, K],  sx fp32 [M]
 //   quant_rows_int8: x bf16 [M, K]  ->  codes int8 [M, K],  sx fp32 [M]
 //   gemm_f8, gemm_i8: out[M, N] = diag(sx) (A[M, K] . W[N, K]^T) diag(sw)
+//   moe_gemm_f8:      gemm_f8 per expert over moe_align's sorted rows (F8Grp below):
+//                     out[p, :] = sx[r(p)] (A[r(p), :] . W[e]^T) sw[e, :],  p in [offs[e], offs[e + 1])
 //
 // One kernel, two operand policies (F8Ops, I8Ops below): the byte images, the staging, the ring
 // and the epilogues do not depend on what a byte means. gemm_i8 reads int8 codes (W as
@@ -145,12 +147,30 @@ __device__ __forceinline__ i32x8_t f8_frag(const uint8_t* row, int g, int sl) {
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <class Ops, int BM, int NS, bool DB>
+// Grouped (MoE expert) form, GRP -- moe_gemm_f8: the M dimension is moe_align's expert-sorted,
+// 64-padded row space [P]; expert e owns rows [offs[e], offs[e + 1]), its own codes w + e N K and
+// its own channel scales sw + e N. Tile slot mi of a column tile is the mi-th (expert, row tile) in
+// expert order, found by walking offs; the slots past the last tile leave as a whole workgroup.
+// They sit at the end of the order, so the tiles go out in plain dispatch order (block b on XCD
+// b % 8 spreads the real tiles over every XCD; the XCD-contiguous order would leave XCDs idle).
+// The A gather moves only source addresses: DMA lane (piece, dr) reads code row rows[p] of its
+// sorted row p (rows == nullptr: row p; -1 = a pad: row 0, finite data never combined), rows at or
+// past the segment end re-read the segment's last row and are not stored, and the epilogue takes
+// the row scale from the same place, sx[rows[p]]. The issue order, and so every wait count, is the
+// dense kernel's.
+struct F8Grp {
+  const int32_t* rows;
+  const int32_t* offs;
+  int E;
+  int mt;  // tile slots per column tile (host bound on the experts' tiles)
+};
+
+template <class Ops, int BM, int NS, bool DB, bool GRP = false>
 __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restrict__ a, const float* __restrict__ sx,
                                                           int M, int K, const uint8_t* __restrict__ w,
                                                           const float* __restrict__ sw, int N, int S,
                                                           float* __restrict__ part, uint16_t* __restrict__ out,
-                                                          int mode) {
+                                                          int mode, F8Grp grp) {
   constexpr int BN = f8::BN;
   constexpr int MT = BM / 32;            // 16-row m tiles per wave
   constexpr int NA = BM / 64;            // A DMA instructions per wave per K tile
@@ -171,13 +191,36 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
   const int nb = gridDim.x, bid = blockIdx.x;
   const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
   const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int per_split = TM * TN;
-  const int s = v / per_split, u = v - s * per_split;
-  const int GM = TM < f8::GROUP_M ? TM : f8::GROUP_M;
-  const int gsz = GM * TN, gid = u / gsz, first_m = gid * GM;
-  const int gm = TM - first_m < GM ? TM - first_m : GM;
-  const int ug = u - gid * gsz;
-  const int m0 = (first_m + ug % gm) * BM, n0 = (ug / gm) * BN;
+  int s, m0, n0, m_hi = M;   // m_hi: one past the last row this tile loads and stores
+  if constexpr (GRP) {
+    const int per_split = grp.mt * TN;
+    s = bid / per_split;
+    const int u = bid - s * per_split, mi = u / TN;
+    n0 = (u - mi * TN) * BN;
+    int e = 0, base = 0, lo = 0, hi = 0;
+    for (; e < grp.E; ++e) {
+      lo = grp.offs[e];
+      hi = grp.offs[e + 1];
+      const int nt = (hi - lo + BM - 1) / BM;
+      if (mi < base + nt) break;
+      base += nt;
+    }
+    if (e == grp.E) return;  // past the last tile: the whole workgroup leaves (uniform)
+    m0 = lo + (mi - base) * BM;   // < hi: the expert has more than mi - base tiles
+    m_hi = hi;
+    w += static_cast<int64_t>(e) * N * K;
+    sw += static_cast<int64_t>(e) * N;
+  } else {
+    const int per_split = TM * TN;
+    s = v / per_split;
+    const int u = v - s * per_split;
+    const int GM = TM < f8::GROUP_M ? TM : f8::GROUP_M;
+    const int gsz = GM * TN, gid = u / gsz, first_m = gid * GM;
+    const int gm = TM - first_m < GM ? TM - first_m : GM;
+    const int ug = u - gid * gsz;
+    m0 = (first_m + ug % gm) * BM;
+    n0 = (ug / gm) * BN;
+  }
   const int nk_all = K / f8::KT;
   const int kt_lo = static_cast<int>(static_cast<int64_t>(s) * nk_all / S);
   const int nk = static_cast<int>(static_cast<int64_t>(s + 1) * nk_all / S) - kt_lo;
@@ -193,7 +236,8 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
   const uint8_t* asrc[NA];
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
-    const int row = min(m0 + 8 * (wid + 8 * i) + dr, M - 1);
+    int row = min(m0 + 8 * (wid + 8 * i) + dr, m_hi - 1);
+    if constexpr (GRP) row = grp.rows != nullptr ? max(grp.rows[row], 0) : row;
     asrc[i] = a + static_cast<int64_t>(row) * K + static_cast<int64_t>(kt_lo) * f8::KT + swz;
   }
   const uint8_t* wsrc = w + static_cast<int64_t>(n0 + 32 * wid + dr) * K + static_cast<int64_t>(kt_lo) * f8::KT + swz;
@@ -289,8 +333,8 @@ __global__ void __launch_bounds__(512, 1) gemm_f8_kernel(const uint8_t* __restri
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     const int m = mb + 16 * mt;
-    if (m >= M) continue;
-    const float rs = sx[m];
+    if (m >= m_hi) continue;
+    const float rs = sx[GRP && grp.rows != nullptr ? max(grp.rows[m], 0) : m];
     float o[4][4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
@@ -466,7 +510,7 @@ static int gemm_8bit(const uint8_t* a, const float* sx, int M, int K, const uint
     static constexpr F8Cfg f = F8_CFGS[decltype(c)::value];
     const int tiles = ((M + f.bm - 1) / f.bm) * (N / f8::BN);
     hipLaunchKernelGGL((gemm_f8_kernel<Ops, f.bm, f.ns, f.bm <= 128>), dim3(tiles * S), dim3(512), 0, st, a, sx, M, K, w, sw, N, S,
-                       part, out, mode);
+                       part, out, mode, F8Grp{});
     rc = static_cast<int>(hipGetLastError());
   });
   return rc;
@@ -480,6 +524,40 @@ int gemm_i8(const uint8_t* a, const float* sx, int M, int K, const uint8_t* w, c
             uint16_t* out, int S, int mode, int cfg, hipStream_t st) {
   if (!i8_supports(M, K, N, S, mode, cfg)) return 1;
   return gemm_8bit<I8Ops>(a, sx, M, K, w, sw, N, part, out, S, mode, cfg, st);
+}
+
+// ---------------------------------------------------------------- moe_gemm_f8 (the grouped form)
+// Tile slots per column tile: the sum over experts of ceil(segment / bm), segments 64-padded, is
+// at most (max_pairs + 63 E) / bm + E.
+static int64_t moe_f8_slots(int E, int max_pairs, int bm) { return (max_pairs + int64_t{63} * E) / bm + E; }
+
+bool moe_f8_supports(int E, int P, int K, int N, int max_pairs, int S, int mode, int cfg) {
+  if (E < 1 || P < 64 || P % 64 || max_pairs < 1 || cfg < 0 || cfg >= F8_NCFG) return false;
+  if (K < f8::KT || K % f8::KT || N < f8::BN || N % f8::BN || S < 1 || S > K / f8::KT) return false;
+  if (moe_f8_slots(E, max_pairs, F8_CFGS[cfg].bm) * (N / f8::BN) * S >= (int64_t{1} << 31)) return false;
+  return mode == F8_PARTIAL || (mode == F8_SILU && S == 1);
+}
+
+// a: E4M3 codes [., K] with one scale per row in sx; rows [P] gathers both (nullptr: they are in
+// sorted order, [P, K] and [P]); offs [E + 1]; w codes [E, N, K], sw [E, N]; max_pairs bounds the
+// real rows over all experts (it sizes the grid). F8_SILU: out bf16 [P, N / 2]; F8_PARTIAL: part
+// fp32 [S, P, N]. Returns 0, or 1 for what it cannot take.
+int moe_gemm_f8(const uint8_t* a, const float* sx, const int32_t* rows, const int32_t* offs, int E, int P, int K,
+                const uint8_t* w, const float* sw, int N, int max_pairs, float* part, uint16_t* out, int S, int mode,
+                int cfg, hipStream_t st) {
+  if (!moe_f8_supports(E, P, K, N, max_pairs, S, mode, cfg)) return 1;
+  if (a == nullptr || sx == nullptr || offs == nullptr || w == nullptr || sw == nullptr) return 1;
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(sw)) & 15) return 1;
+  if (mode == F8_PARTIAL ? part == nullptr : out == nullptr) return 1;
+  int rc = 1;
+  cfg_dispatch<F8_NCFG>(cfg, [&](auto c) {
+    static constexpr F8Cfg f = F8_CFGS[decltype(c)::value];
+    const int mt = static_cast<int>(moe_f8_slots(E, max_pairs, f.bm));
+    hipLaunchKernelGGL((gemm_f8_kernel<F8Ops, f.bm, f.ns, f.bm <= 128, true>), dim3(mt * (N / f8::BN) * S), dim3(512), 0,
+                       st, a, sx, P, K, w, sw, N, S, part, out, mode, F8Grp{rows, offs, E, mt});
+    rc = static_cast<int>(hipGetLastError());
+  });
+  return rc;
 }
 
 }  // namespace xgk

@@ -467,6 +467,15 @@ PYBIND11_MODULE(_kernels, m) {
                                max_pairs, P<float>(part), P<uint16_t>(out), splits, mode, cfg, S(st)),
           "gemm_pf_grouped");
   });
+  // gemm_f8's grouped form: the prompt-sized expert GEMMs on fp8 expert codes
+  m.def("moe_gemm_f8", [](uintptr_t a, uintptr_t sx, uintptr_t rows, uintptr_t offs, int E, int n_rows, int K,
+                          uintptr_t w, uintptr_t sw, int N, int max_pairs, uintptr_t part, uintptr_t out, int splits,
+                          int mode, int cfg, uintptr_t st) {
+    check(xgk::moe_gemm_f8(P<const uint8_t>(a), P<const float>(sx), P<const int32_t>(rows), P<const int32_t>(offs), E,
+                           n_rows, K, P<const uint8_t>(w), P<const float>(sw), N, max_pairs, P<float>(part),
+                           P<uint16_t>(out), splits, mode, cfg, S(st)),
+          "moe_gemm_f8");
+  });
   // FP8 x FP8 prompt-sized GEMM and its row quantizer (gemm_f8.hip)
   m.def("gemm_f8", [](uintptr_t a, uintptr_t sx, int M, int K, uintptr_t w, uintptr_t sw, int N, uintptr_t part,
                       uintptr_t out, int splits, int mode, int cfg, uintptr_t st) {
@@ -591,6 +600,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("pf_supports", &xgk::pf_supports);
   m.def("pf_grouped_supports", &xgk::pf_grouped_supports);
   m.def("f8_supports", &xgk::f8_supports);
+  m.def("moe_f8_supports", &xgk::moe_f8_supports);
   m.def("i8_supports", &xgk::i8_supports);
   m.def("i4_supports", &xgk::i4_supports);
   m.def("add_partials_resid", [](uintptr_t part, int S_, int T, uintptr_t res, uintptr_t ss_part, int H,

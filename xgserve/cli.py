@@ -37,6 +37,9 @@ def _common(p: argparse.ArgumentParser) -> None:
                    help="with fp8|int8|int4: release the bf16 projection weights and serve from the quantized ones alone")
     p.add_argument("--fp8-activations", action="store_true", default=None,
                    help="with fp8, tp 1: prompt steps above 320 rows quantize activations per token (FP8 matrix instructions)")
+    p.add_argument("--fp8-expert-activations", action="store_true", default=None,
+                   help="with fp8, tp 1, Mixtral: prompt steps above 256 token-expert pairs run the experts on their "
+                        "fp8 codes with activations quantized per token (FP8 matrix instructions)")
     p.add_argument("--int8-activations", action="store_true", default=None,
                    help="with int8 or int4, tp 1: prompt steps above 320 rows quantize activations per token (INT8 matrix instructions)")
     p.add_argument("--strategy", choices=["round_robin", "least_loaded", "memory_aware"])
@@ -58,6 +61,7 @@ def _overrides(a) -> dict:
         "worker": {"model": a.model, "checkpoint": a.checkpoint, "tp": a.tp, "replicas": a.replicas, "gpus": a.gpus,
                    "device": a.device, "quantization": a.quantization, "quantized_only": a.quantized_only,
                    "fp8_activations": a.fp8_activations, "int8_activations": a.int8_activations,
+                   "fp8_expert_activations": a.fp8_expert_activations,
                    "max_num_seqs": a.max_num_seqs,
                    "max_model_len": a.max_model_len, "mock": a.mock, "in_process": a.in_process,
                    "use_graphs": (False if a.no_graphs else None),

@@ -133,6 +133,9 @@ class EngineConfig:
     # the same for int8 and int4 models: per-token int8 codes on the INT8 matrix instructions
     # (gemm_i8; int4 weights: gemm_i4)
     int8_activations: bool = False
+    # fp8 Mixtral (TP = 1, GPU): prompt steps above 256 token-expert pairs run the expert GEMMs on the
+    # fp8 expert codes with per-token E4M3 activations (moe_gemm_f8); outputs differ from weight-only
+    fp8_expert_activations: bool = False
     # custom xGMI all-reduce peer-wait limit while serving: a TP peer this late fails
     # the step (CustomAllReduceTimeout -> replica restart); warmup runs under 20 s
     collective_timeout_s: float = 2.0
@@ -163,7 +166,8 @@ class LLMEngine:
                                                                  weight_dtype=cfg.weight_dtype,
                                                                  quantized_only=cfg.quantized_only, mw8=cfg.mw8,
                                                                  a8=cfg.fp8_activations,
-                                                                 ai8=cfg.int8_activations)
+                                                                 ai8=cfg.int8_activations,
+                                                                 ea8=cfg.fp8_expert_activations)
         self.model.set_moe_comm(cfg.moe_comm)
         # static after load: resident weight bytes (parameters + quantized copies) and the
         # quantized-only dequantization scratch, reported by stats()
@@ -1005,6 +1009,7 @@ class LLMEngine:
             "scratch_bytes": self._scratch_bytes + (self.spec.scratch_bytes() if self.spec is not None else 0),
             "weight_dtype": getattr(self.model, "weight_dtype", None) or str(self.model.dtype).replace("torch.", ""),
             "activation_dtype": "fp8" if self.cfg.fp8_activations else "int8" if self.cfg.int8_activations else "bf16",
+            "expert_activation_dtype": "fp8" if self.cfg.fp8_expert_activations else "bf16",
             "cache": cs,
             "preemptions": self.sched.total_preemptions(),
             **self.stats_counters,

@@ -54,7 +54,7 @@ from ..ops.linear import (MODE_BF16, MODE_PARTIAL, MODE_SILU, MW_MAX_M, W8_MAX_M
                           f8_linear, f8_plan, i4_linear, i4_plan, i8_linear, i8_plan, mw8_linear, mw8_plan, mw_linear, mw_plan, pf_linear, pf_plan,
                           quantize_expert_stack, quantize_fp8, quantize_weight, skinny_linear, splitk_linear, splitk_prefill_ok, w8_linear,
                           w8_plan, WQ_FORMATS)
-from ..ops.moe import moe_w8_plan
+from ..ops.moe import MOE_PREFILL_PAIRS, moe_f8_plan, moe_w8_plan
 from .base import AttnMeta, PagedAttention, init_weight, kv_head_range, local_heads, shard
 from .config import ModelConfig
 
@@ -351,6 +351,7 @@ class LlamaLayer(nn.Module):
         self.attn = PagedAttention(Hq, Hkv, D)
         self.moe_comm = "auto"
         self.w8 = None  # fp8 / int8 / int4 weight copies for decode (LlamaForCausalLM.quantize_weights)
+        self.ea8 = False  # MoE: steps above MOE_PREFILL_PAIRS pairs run the experts on fp8 codes (quantize_weights ea8)
         # quantized_only: the model's bf16 scratch that "dq" steps dequantize one projection
         # into, and the [N, K] of each projection whose bf16 weight was released
         self.dq_scratch: Optional[torch.Tensor] = None
@@ -406,12 +407,14 @@ class LlamaLayer(nn.Module):
         return skinny_linear(x, w, None, mode)
 
     # ------------------------------------------------------------------ MoE
-    def _moe_allreduce(self, h: torch.Tensor, codes: bool = False) -> torch.Tensor:
+    def _moe_allreduce(self, h: torch.Tensor, codes: bool = False, ea8: bool = False) -> torch.Tensor:
         w, ids = ops.moe_route(h, self.router, self.cfg.experts_per_token)
-        # codes: the step reads the experts' quantized copies on moe_gemm_w8
-        wq = self.w8["w13"][:2] + self.w8["w2"] if codes else None
+        # codes: the step reads the experts' quantized copies on moe_gemm_w8; ea8: a step above
+        # MOE_PREFILL_PAIRS pairs reads them on moe_gemm_f8 (smaller ones keep their kernels of today)
+        ea8 = ea8 and ids.numel() > MOE_PREFILL_PAIRS
+        wq = self.w8["w13"][:2] + self.w8["w2"] if codes or ea8 else None
         out = ops.fused_moe(h, self.w13, self.w2, w, ids, self.expert_offset,
-                              experts_total=self.router.shape[0], wq=wq)
+                              experts_total=self.router.shape[0], wq=wq, expert_a8=ea8)
         return self._ar(out)
 
     def _moe_alltoall(self, h: torch.Tensor) -> torch.Tensor:
@@ -509,13 +512,14 @@ class LlamaLayer(nn.Module):
         # the partial output is a fresh contiguous [T, H] bf16 tensor like h
         return not (h.shape[0] <= EP_AR_MAX_TOKENS and ar is not None and ar.can_run(h.contiguous()))
 
-    def mlp(self, h: torch.Tensor, codes: bool = False) -> torch.Tensor:
+    def mlp(self, h: torch.Tensor, codes: bool = False, ea8: bool = False) -> torch.Tensor:
         """The experts of a MoE layer (a dense layer's MLP is the tail of `forward`).
         codes: the quantized step of a quantized model (TP = 1) -- the experts run on their
-        fp8 / int8 / int4 copies."""
+        fp8 / int8 / int4 copies. ea8: fp8 expert activations (TP = 1) -- a prompt-sized step
+        runs them on the fp8 copies and per-token E4M3 activations."""
         if self.tp > 1 and self._moe_use_alltoall(h):
             return self._moe_alltoall(h)
-        return self._moe_allreduce(h, codes)
+        return self._moe_allreduce(h, codes, ea8)
 
     def forward(self, x, residual: Optional[torch.Tensor], meta: AttnMeta,
                 kv: Tuple[torch.Tensor, torch.Tensor], cos_sin: torch.Tensor):
@@ -541,7 +545,11 @@ class LlamaLayer(nn.Module):
         h, residual = ops.fused_add_rmsnorm(o, residual, self.post_norm, eps)
         if self.moe:
             # the experts switch to their codes where the attention projections do
-            return self.mlp(h, codes=step is self.dispatch.quantized and "w13" in (self.w8 or {})), residual
+            # ea8: prompt steps only -- a pure decode step keeps its kernels however many rows it has
+            # (129 sequences are already 258 pairs), and the runner's mixed-step graph bodies keep
+            # their families, as for "f8"
+            return self.mlp(h, codes=step is self.dispatch.quantized and "w13" in (self.w8 or {}),
+                            ea8=self.ea8 and meta.num_decodes < T and not meta.mixed_graph), residual
         if step.gate_up in ("lib", "dq"):  # bf16 gate|up rows out of the library GEMM
             act = ops.silu_and_mul(self._gemm(step.gate_up, h, "gate_up", MODE_BF16), interleave16=True)
         else:
@@ -700,7 +708,7 @@ class LlamaForCausalLM(nn.Module):
 
     @torch.no_grad()
     def quantize_weights(self, kind: str = "fp8", quantized_only: bool = False, mw8: bool = False,
-                         a8: bool = False, ai8: bool = False) -> bool:
+                         a8: bool = False, ai8: bool = False, ea8: bool = False) -> bool:
         """Weight-only quantization for decode batches <= 64 (Req 10.3): per dense
         layer, copies of the QKV / O / gate_up / down weights (unfolded:
         build_model keeps the RMSNorm weights in the norms of a quantized model)
@@ -739,10 +747,24 @@ class LlamaForCausalLM(nn.Module):
         weight-only model's. Smaller steps stay weight-only.
         ai8 (EngineConfig.int8_activations): the same for int8 models -- per-token int8 codes,
         i8_plan, the INT8 matrix instructions (gemm_i8) -- and for int4 models: the same codes
-        against the packed int4 weights, i4_plan, gemm_i4 (one int32 sum per 128-k scale group)."""
+        against the packed int4 weights, i4_plan, gemm_i4 (one int32 sum per 128-k scale group).
+        ea8 (EngineConfig.fp8_expert_activations; fp8, TP = 1, Mixtral on a GPU, not
+        quantized_only, expert shapes with a moe_f8_plan -- anything else raises): steps above
+        MOE_PREFILL_PAIRS token-expert pairs (not the mixed-step graph bodies) quantize the
+        experts' input and the gated activation per token to E4M3 and run both expert GEMMs on
+        the fp8 expert copies (moe_gemm_f8). Outputs then differ from the weight-only model's.
+        QKV / O, smaller steps and every decode step stay as they are."""
         fmt = WQ_FORMATS[kind]
         l0 = self.layers[0]
         moe = any(l.moe for l in self.layers)
+        if ea8:
+            why = [t for c, t in ((kind != "fp8", f"fp8 weights, not {kind}"), (self.tp != 1, "TP = 1"),
+                                  (not moe, "Mixtral (a dense model takes a8)"), (self.device.type != "cuda", "a GPU"),
+                                  (quantized_only, "the resident bf16 experts (not quantized_only)")) if c]
+            if not why and moe_f8_plan(MOE_PREFILL_PAIRS + 1, l0.w13.shape[0], l0.w13.shape[2], l0.w13.shape[1] // 2) is None:
+                why = [f"expert shapes that moe_gemm_f8 takes, not H={l0.w13.shape[2]} F={l0.w13.shape[1] // 2}"]
+            if why:
+                raise ValueError("fp8 expert activations (ea8) need " + ", ".join(why))
         for on, key, need in ((a8, "a8", ("fp8",)), (ai8, "ai8", ("int8", "int4"))):
             if on:
                 why = [t for c, t in ((kind not in need, f"{' or '.join(need)} weights, not {kind}"), (self.tp != 1, "TP = 1"),
@@ -772,6 +794,7 @@ class LlamaForCausalLM(nn.Module):
             l.w8 = {n: quantize_weight(getattr(l, n), fmt) + (fmt,) for n in chosen}
             if l.moe:  # expert copies beside the resident bf16 experts (which larger steps read)
                 l.w8.update({n: quantize_expert_stack(getattr(l, n), fmt) + (fmt,) for n in ("w13", "w2")})
+                l.ea8 = ea8
             l.dispatch.set_quantized(chosen, resident=not quantized_only, fmt=fmt if mw8 else None, a8=a8, a8_fmt=fmt,
                                      ai8=ai8, ai8_fmt=fmt, aw4=ai8, aw4_fmt=fmt)
             if quantized_only:

@@ -30,7 +30,7 @@ def model_class(cfg: ModelConfig):
 def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = None,
                 checkpoint: Optional[str] = None, seed: int = 0, tp: Optional[int] = None,
                 rank: Optional[int] = None, weight_dtype: Optional[str] = None, quantized_only: bool = False,
-                mw8: bool = False, a8: bool = False, ai8: bool = False):
+                mw8: bool = False, a8: bool = False, ai8: bool = False, ea8: bool = False):
     """weight_dtype "fp8" / "int8" / "int4": also keep quantized weight copies for
     decode batches <= 64 (LlamaForCausalLM.quantize_weights); activations and
     everything else stay `dtype`. quantized_only: keep ONLY the quantized projection
@@ -39,7 +39,10 @@ def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = N
     (LlamaForCausalLM.quantize_weights). a8: fp8 activations on prompt steps above 320 rows
     (gemm_f8; fp8 weights, TP = 1, dense models on a GPU -- anything else raises). ai8: int8
     activations on the same steps of an int8 model (gemm_i8; the same conditions) or of an int4 model
-    (gemm_i4)."""
+    (gemm_i4). ea8: fp8 expert activations on prompt steps above 256 token-expert pairs of an fp8
+    Mixtral (moe_gemm_f8; TP = 1, on a GPU, not quantized_only -- anything else raises)."""
+    if ea8 and weight_dtype != "fp8":
+        raise ValueError(f"fp8 expert activations (ea8) need weight_dtype fp8, got {weight_dtype!r}")
     if ai8 and weight_dtype not in ("int8", "int4"):
         raise ValueError(f"int8 activations (ai8) need weight_dtype int8 or int4, got {weight_dtype!r}")
     if a8 and weight_dtype != "fp8":
@@ -63,7 +66,8 @@ def build_model(cfg: ModelConfig, device="cpu", dtype: Optional[torch.dtype] = N
     if weight_dtype in ("fp8", "int8", "int4"):
         if not (hasattr(m, "quantize_weights")
                 and m.quantize_weights(weight_dtype, quantized_only=quantized_only, mw8=mw8,
-                                       **({"a8": True} if a8 else {}), **({"ai8": True} if ai8 else {}))):
+                                       **({"a8": True} if a8 else {}), **({"ai8": True} if ai8 else {}),
+                                       **({"ea8": True} if ea8 else {}))):
             raise ValueError(f"{weight_dtype} weights are not supported for {cfg.name} on {device}")
     elif weight_dtype not in (None, "bf16", "fp16", "fp32"):
         raise ValueError(f"unknown weight_dtype {weight_dtype!r}")

@@ -7,7 +7,8 @@ import torch
 
 from ._native import kernels, stream_ptr, use_native
 from .activation import silu_and_mul
-from .linear import M64G_CFGS, MODE_PARTIAL, MODE_SILU, WQ_FP8, WQ_GROUP, WQ_INT4, WQ_INT8, WQ_SC_FLOATS
+from .linear import (F8_CFGS, F8_COLS, F8_KT, F8_QUANT_MAX_K, M64G_CFGS, MODE_PARTIAL, MODE_SILU, WQ_FP8, WQ_GROUP,
+                     WQ_INT4, WQ_INT8, WQ_SC_FLOATS, quant_rows_fp8)
 
 BLOCK_M = 64
 # gemm_m64g launch configurations for the expert GEMMs (see ops/linear.py M64G_CFGS);
@@ -120,6 +121,64 @@ def moe_w8_plan(pairs: int, E: int, H: int, F: int, fmt: int):
     w2 = next(((c, S) for c in (c2, 2, 1, 0) for S in splits if _moe_w8_fits(H, F, MODE_PARTIAL, S, c, pairs, fmt)),
               None)
     return None if cfg13 is None or w2 is None else (cfg13, w2[0], w2[1])
+
+
+# csrc/kernels/gemm_f8.hip moe_gemm_f8: the grouped GEMMs of a prompt-sized step (more than
+# MOE_PREFILL_PAIRS pairs) on fp8 expert codes and per-token E4M3 activations (fused_moe(wq=...,
+# expert_a8=True)). The constants of moe_f8_plan:
+MOE_F8_BM128_ROWS = 128  # a 64-padded average segment up to this many rows runs the 128-row tiles
+MOE_F8_CUS = 256         # workgroups of one round (one 512-thread workgroup per CU)
+
+
+def _moe_f8_fits(K: int, N: int, S: int, mode: int, cfg: int) -> bool:
+    """The shape half of the library's moe_f8_supports (E, P and the grid size aside)."""
+    if cfg not in F8_CFGS or K < F8_KT or K % F8_KT or N < F8_COLS or N % F8_COLS or not 1 <= S <= K // F8_KT:
+        return False
+    return mode == MODE_PARTIAL or (mode == MODE_SILU and S == 1)
+
+
+def moe_f8_plan(pairs: int, E: int, H: int, F: int, experts_total: Optional[int] = None):
+    """moe_gemm_f8 configurations of a step's expert GEMMs (pairs = token-expert pairs, E local
+    experts): (cfg of w13 [2F, H] with the SiLU gate, cfg of w2 [H, F], K splits of w2), or None
+    -- at most MOE_PREFILL_PAIRS pairs (those steps keep moe_gemm_w8 / gemm_m64g), or a shape
+    that moe_gemm_f8 or the row quantizer (rows of H and of F elements) does not take. The
+    lower bound is not a crossover: at Mixtral 8x7B shapes the path measured 1.35-1.92x ahead of
+    gemm_pf_grouped at 512 / 1,150 / 4,096 / 16,000 pairs (profiles/moe_f8.md). A rule, nothing
+    was swept:
+      * the tile. seg = this rank's expected pairs per expert (pairs * E / experts_total under
+        EP), padded to 64 as moe_align pads a segment. seg <= MOE_F8_BM128_ROWS = 128: the
+        128-row tiles (F8_CFGS 1) -- a 256-row tile over such a segment is at least half
+        padding, twice the matrix instructions for the same rows. Above: the 256-row tiles
+        (F8_CFGS 0), which read 0.375 LDS fragments per matrix instruction against 0.5 and are
+        the faster tile of dense gemm_f8 wherever they fill. Both GEMMs share the row space, so
+        they share the cfg.
+      * the split of w2. It has only H / 256 column tiles per row tile: with fewer workgroups
+        than MOE_F8_CUS = 256 (one per CU of an MI355X) half the chip would idle, so K is split
+        in 2 (the combine reduces the slabs, as on the bf16 path) -- where each split keeps at
+        least two K tiles (F >= 512), as f8_plan asks."""
+    if pairs <= MOE_PREFILL_PAIRS or E < 1 or max(H, F) > F8_QUANT_MAX_K:
+        return None
+    share = pairs * E // experts_total if experts_total else pairs
+    seg = -(-max(1, share // E) // BLOCK_M) * BLOCK_M
+    cfg = 1 if seg <= MOE_F8_BM128_ROWS else 0
+    bm = F8_CFGS[cfg][0]
+    S = 2 if E * -(-seg // bm) * (H // F8_COLS) < MOE_F8_CUS and F // (2 * F8_KT) >= 2 else 1
+    if not (_moe_f8_fits(H, 2 * F, 1, MODE_SILU, cfg) and _moe_f8_fits(F, H, S, MODE_PARTIAL, cfg)):
+        return None
+    return cfg, cfg, S
+
+
+def _wq_ok(wq, E: int, F2: int, H: int, x: torch.Tensor) -> bool:
+    """wq's tensors are quantize_expert_stack's of w13 [E, F2, H] and w2 [E, H, F2 / 2], on x's device."""
+    q13, s13, q2, s2, fmt = wq
+    F = F2 // 2
+    kw = 2 if fmt == WQ_INT4 else 1  # codes per byte
+    return (q13.dtype == torch.uint8 and q2.dtype == torch.uint8
+            and tuple(q13.shape) == (E, F2, H // kw) and tuple(q2.shape) == (E, H, F // kw)
+            and s13.dtype == torch.float32 and s2.dtype == torch.float32
+            and s13.numel() == E * F2 * (H // WQ_GROUP if fmt == WQ_INT4 else 1)
+            and s2.numel() == E * H * (F // WQ_GROUP if fmt == WQ_INT4 else 1)
+            and all(t.is_contiguous() and t.device == x.device for t in (q13, s13, q2, s2)))
 
 
 def _moe_pf_ok(H: int, F: int) -> bool:
@@ -235,7 +294,8 @@ def moe_forward_ref(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w
 def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torch.Tensor,
               topk_ids: torch.Tensor, expert_offset: int = 0, resid: Optional[torch.Tensor] = None,
               ss: Optional[torch.Tensor] = None, out_f32: bool = False, layout=None,
-              counters: Optional[torch.Tensor] = None, experts_total: Optional[int] = None, wq=None):
+              counters: Optional[torch.Tensor] = None, experts_total: Optional[int] = None, wq=None,
+              expert_a8: bool = False):
     """Local-expert MoE FFN: sum_j w_j * FFN_{e_j}(x) over choices owned locally
     (ids in [expert_offset, expert_offset + E_local)); others contribute nothing.
 
@@ -255,7 +315,12 @@ def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torc
     w13 and w2): a step of at most MOE_PREFILL_PAIRS pairs on a GPU reads the codes
     instead -- align -> moe_gemm_w8 on w13 (SiLU gate) -> moe_gemm_w8 on w2 (split-K
     partials) -> the separate combine (no in-launch combine on codes); a shape without
-    a moe_w8_plan raises. Larger steps, and the CPU reference, read w13 / w2."""
+    a moe_w8_plan raises. Larger steps, and the CPU reference, read w13 / w2.
+    expert_a8 (with fp8 codes in wq, bf16 x, on a GPU): a step of more than MOE_PREFILL_PAIRS
+    pairs that has a moe_f8_plan runs on the codes too, with its activations quantized per row
+    to E4M3 -- quant_rows_fp8(x) -> moe_gemm_f8 on w13 (gathered, SiLU gate) ->
+    quant_rows_fp8(act) -> moe_gemm_f8 on w2 (split-K partials) -> the combine. Its result
+    differs from the bf16 experts' (W8A8). Without it, and for every smaller step, nothing changes."""
     if not use_native(x):
         out = moe_forward_ref(x, w13, w2, topk_w, topk_ids, expert_offset)
         if resid is None:
@@ -279,13 +344,7 @@ def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torc
     if wq is not None and max_rows <= MOE_PREFILL_PAIRS:
         q13, s13, q2, s2, fmt = wq
         plan = moe_w8_plan(max_rows, E, H, F, fmt)
-        kw = 2 if fmt == WQ_INT4 else 1  # codes per byte
-        if (plan is None or q13.dtype != torch.uint8 or q2.dtype != torch.uint8
-                or tuple(q13.shape) != (E, F2, H // kw) or tuple(q2.shape) != (E, H, F // kw)
-                or s13.dtype != torch.float32 or s2.dtype != torch.float32
-                or s13.numel() != E * F2 * (H // WQ_GROUP if fmt == WQ_INT4 else 1)
-                or s2.numel() != E * H * (F // WQ_GROUP if fmt == WQ_INT4 else 1)
-                or not all(t.is_contiguous() and t.device == x.device for t in (q13, s13, q2, s2))):
+        if plan is None or not _wq_ok(wq, E, F2, H, x):
             raise ValueError(f"moe_gemm_w8: unsupported experts E={E} H={H} F={F} fmt={fmt} pairs={max_rows}")
         cfg13, cfg2, S = plan
         kn.moe_gemm_w8(x.contiguous().data_ptr(), sorted_rows.data_ptr(), offs.data_ptr(), E, H, q13.data_ptr(),
@@ -294,6 +353,24 @@ def fused_moe(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_w: torc
         part = torch.empty(S, P, H, dtype=torch.float32, device=x.device)
         kn.moe_gemm_w8(act.data_ptr(), 0, offs.data_ptr(), E, F, q2.data_ptr(), s2.data_ptr(), H, P, part.data_ptr(),
                        0, S, MODE_PARTIAL, cfg2, fmt, max_rows, stream_ptr(), valid, T * k)
+        return _moe_combine(kn, part, S, P, dest, topk_w, resid, ss, T, k, H, x, out_f32)
+
+    f8p = (moe_f8_plan(max_rows, E, H, F, experts_total)
+           if expert_a8 and wq is not None and wq[4] == WQ_FP8 and x.dtype == torch.bfloat16 else None)
+    if f8p is not None:
+        if not _wq_ok(wq, E, F2, H, x):
+            raise ValueError(f"moe_gemm_f8: unsupported experts E={E} H={H} F={F} pairs={max_rows}")
+        q13, s13, q2, s2, _ = wq
+        cfg13, cfg2, S = f8p
+        a, sx = quant_rows_fp8(x.contiguous())  # once per step: every expert reads the same row codes
+        kn.moe_gemm_f8(a.data_ptr(), sx.data_ptr(), sorted_rows.data_ptr(), offs.data_ptr(), E, P, H, q13.data_ptr(),
+                       s13.data_ptr(), F2, max_rows, 0, act.data_ptr(), 1, MODE_SILU, cfg13, stream_ptr())
+        # all P rows: the rows past offs[E] were never written, so their codes and scales are
+        # garbage -- which no tile of the w2 launch reads (its rows end at offs[E])
+        a2, sx2 = quant_rows_fp8(act)
+        part = torch.empty(S, P, H, dtype=torch.float32, device=x.device)
+        kn.moe_gemm_f8(a2.data_ptr(), sx2.data_ptr(), 0, offs.data_ptr(), E, P, F, q2.data_ptr(), s2.data_ptr(), H,
+                       max_rows, part.data_ptr(), 0, S, MODE_PARTIAL, cfg2, stream_ptr())
         return _moe_combine(kn, part, S, P, dest, topk_w, resid, ss, T, k, H, x, out_f32)
 
     if MOE_PF and max_rows > MOE_PREFILL_PAIRS and _moe_pf_ok(H, F):

@@ -115,6 +115,11 @@ class WorkerSection:
     # the same with quantization int8 (gemm_i8) or int4 (gemm_i4): per-token int8 codes on the INT8
     # matrix instructions
     int8_activations: bool = False
+    # with quantization fp8, tp 1, Mixtral on a GPU (not quantized_only): prompt steps above 256
+    # token-expert pairs run the expert GEMMs on the fp8 expert copies with activations quantized per
+    # token to E4M3 (moe_gemm_f8), so outputs differ from the weight-only server's; QKV / O, smaller
+    # steps and every decode step stay as they are
+    fp8_expert_activations: bool = False
     block_size: int = 16
     max_num_seqs: int = 256
     max_num_batched_tokens: int = 8192
@@ -242,6 +247,23 @@ class ServerConfig:
                     from ..models.config import get_config
                     if get_config(w.checkpoint or w.model).arch == "mixtral":
                         e.append(f"worker.{key} does not cover Mixtral (dense Llama models only)")
+                except Exception:  # (an unknown model is reported below)
+                    pass
+        if w.fp8_expert_activations:
+            key = "worker.fp8_expert_activations"
+            if w.quantization != "fp8":
+                e.append(f"{key} needs worker.quantization fp8, got {w.quantization!r}")
+            if w.device == "cpu":
+                e.append(f"{key} needs a GPU (worker.device is cpu)")
+            if w.tp != 1:
+                e.append(f"{key} needs worker.tp = 1, got {w.tp}")
+            if w.quantized_only:
+                e.append(f"{key} cannot be combined with worker.quantized_only (prompt steps of Mixtral read the bf16 experts)")
+            if not w.mock:
+                try:
+                    from ..models.config import get_config
+                    if get_config(w.checkpoint or w.model).arch != "mixtral":
+                        e.append(f"{key} covers Mixtral only (a dense model takes worker.fp8_activations)")
                 except Exception:  # (an unknown model is reported below)
                     pass
         if not (0.0 < w.gpu_memory_utilization <= 1.0):

@@ -1027,6 +1027,7 @@ class InferenceServer:
                          "weight_bytes": st.get("weight_bytes", 0), "scratch_bytes": st.get("scratch_bytes", 0),
                          "weight_dtype": st.get("weight_dtype"),
                          "activation_dtype": st.get("activation_dtype", "bf16"),
+                         "expert_activation_dtype": st.get("expert_activation_dtype", "bf16"),
                          "kind": r.kind if r else None, "restarts": r.restarts if r else 0,
                          "requests_dispatched": self.dispatched.get(s["id"], 0),
                          "heartbeat_age_s": r.heartbeat_age() if r else None, "engine": st})

@@ -48,6 +48,7 @@ def engine_spec(worker, cache=None, spec=None, fault: Optional[dict] = None, bat
                 checkpoint=worker.checkpoint, tp=worker.tp, device=worker.device, dtype=dt, weight_dtype=wdt,
                 quantized_only=worker.quantized_only, fp8_activations=bool(getattr(worker, "fp8_activations", False)),
                 int8_activations=bool(getattr(worker, "int8_activations", False)),
+                fp8_expert_activations=bool(getattr(worker, "fp8_expert_activations", False)),
                 block_size=worker.block_size, max_num_seqs=worker.max_num_seqs,
                 max_num_batched_tokens=worker.max_num_batched_tokens, max_model_len=worker.max_model_len,
                 gpu_memory_utilization=worker.gpu_memory_utilization, num_blocks=worker.num_blocks,
